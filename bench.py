@@ -1,9 +1,14 @@
 #!/usr/bin/env python3
 """Headline benchmark: DAE training cubes/s at |V|=22,000, d=256, B=512/GPU, BCE only, bf16
-(BASELINE.json configs[1]) on synthetic cubes, plus the recommend p50/p99 latency (configs[0]
-architecture: |V|=20,884, d=512, fp32, model resident).
+(BASELINE.json configs[1]) on synthetic cubes, plus (--full) the recommend p50/p99 latency
+(configs[0] architecture: |V|=20,884, d=512, fp32, model resident).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
+A plain run sets up, warms up, times the K steps and prints the result line (the headline figure
+and ms_per_step).  --dump-outputs DIR also writes what the last timed step left (dump_outputs).
+--full adds everything else the line can carry: the per-kernel durations and rooflines (extra
+steps after the timed region), the data-parallel exchange report, the recommend latency and the
+CPU baseline.
 N>1 is launched by torch.distributed.run (one rank per GPU, RCCL); cubes shard data-parallel
 (weak scaling: B=512 per rank), gradients are all-reduced.  Rank 0 prints ONE JSON line.
 """
@@ -27,6 +32,14 @@ def parse():
     ap.add_argument('--gpus', type=int, default=1)
     ap.add_argument('--steps', type=int, default=200)
     ap.add_argument('--warmup', type=int, default=20)
+    ap.add_argument('--full', action='store_true',
+                    help='after the timed steps also measure what the headline figure does not need: '
+                         'per-kernel durations and rooflines, the data-parallel exchange report, the '
+                         'recommend latency (--no-recommend skips it) and the CPU baseline '
+                         '(--no-cpu-baseline skips it)')
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                    help='after the timed steps write what the last of them computed (the updated '
+                         'parameters, the step\'s losses) as DIR/<name>.npy')
     ap.add_argument('--wo-tower-frac', type=float, default=-1.0,
                     help="the trailing fraction of Wo's Adam run in the tower backward launch (-1: TrainConfig's default)")
     ap.add_argument('--f-in-tower', type=int, default=0,
@@ -469,6 +482,61 @@ def cold_load(flat, lay, V, d, rng):
         shutil.rmtree(tmp, ignore_errors=True)
 
 
+DUMP_BUDGET_BYTES = 48 << 20    # --dump-outputs writes at most this much (fp32 samples of larger outputs)
+
+
+def dump_outputs(tr, out_dir, write):
+    """What a caller of the timed path holds after its last step: every trained parameter tensor
+    (fp32 masters, by its checkpoint name with '/' written '.') and the step's losses
+    (losses.npy: bce, kl, loss in float64).  Outputs beyond DUMP_BUDGET_BYTES in all are written as
+    a fixed sample: the same seeded, sorted element indices of every tensor's flattened form on
+    every run.  Every rank calls this (flush can hold a collective); `write` is rank 0's."""
+    tr.flush()
+    torch.cuda.synchronize()
+    if not write:
+        return
+    arrays = {name.replace('/', '.'): np.ascontiguousarray(a, dtype=np.float32)
+              for name, a in tr.params_dict().items()
+              if tr.use_reg or not name.startswith('decoder_for_reg/')}   # (untrained without reg)
+    frac = min(1.0, DUMP_BUDGET_BYTES / sum(a.nbytes for a in arrays.values()))
+    rng = np.random.default_rng(20250301)
+    os.makedirs(out_dir, exist_ok=True)
+    for name in sorted(arrays):
+        a = arrays[name]
+        if frac < 1.0 and a.size > 4096:
+            a = a.ravel()[np.sort(rng.choice(a.size, max(4096, int(a.size * frac)), replace=False))]
+        np.save(os.path.join(out_dir, name + '.npy'), a)
+    l = tr.losses()
+    np.save(os.path.join(out_dir, 'losses.npy'), np.array([l['bce'], l['kl'], l['loss']], dtype=np.float64))
+
+
+def full_report(out, args, tr, ktimes, dp_report, world):
+    """--full: the rooflines from kernel_profile's durations, the data-parallel exchange report,
+    the recommend latency and the CPU baseline, added to the result line `out` (rank 0)."""
+    kr = kernel_rooflines(tr, ktimes, args.traffic_json)
+    if tr.dp:   # the sharded Adam: this rank's 1/world shard of every bucket, per step
+        ev = dp_report.pop('_adam')
+        kr.append(ev)
+        kr.sort(key=lambda r: -r['avg_us'])
+    roof = dict(kr[0]) if kr else {'bound': 'hbm', 'achieved': None, 'peak': HBM_PEAK_GBS, 'unit': 'GB/s',
+                                   'frac': None, 'traffic': None}
+    roof['measured'] = ('the step\'s longest kernel with a stated algorithmic cost; its average duration from '
+                        'HIP events on its stream around the kernels of eager steps queued behind whole-step '
+                        'graph replays, after the timed region (bench.kernel_profile); the timed region '
+                        'replays graphs only')
+    roof['others'] = [{k: r[k] for k in ('tick', 'kernel', 'bound', 'achieved', 'unit', 'frac', 'avg_us', 'traffic')}
+                      for r in kr[1:]]
+    out['roofline'] = roof
+    out['step_roofline'] = step_roofline(tr, out['ms_per_step'], ktimes)
+    out['kernel_us'] = ktimes
+    if tr.dp:
+        out['dp'] = dp_report
+    if not args.no_recommend and world == 1:
+        out['recommend'] = recommend_latency()
+    if not args.no_cpu_baseline and world == 1:
+        out['cpu_baseline'] = cpu_baseline(args)
+
+
 def main():
     args = parse()
     launch_ranks(args)
@@ -567,29 +635,20 @@ def main():
         dt = float(t.item())
     tr.check_status()
     losses = tr.losses()
-    # per-kernel steady-state times (HIP events; with DP the collectives and the sharded Adam run
-    # between the ticked kernels and are not in them): every rank runs the same extra steps
-    ktimes = kernel_profile(tr, step)
-    dp_report = dp_profile(tr, step) if dp else None
+    if args.dump_outputs:
+        dump_outputs(tr, args.dump_outputs, write=rank == 0)
+    ktimes = dp_report = None
+    if args.full:
+        # per-kernel steady-state times (HIP events; with DP the collectives and the sharded Adam run
+        # between the ticked kernels and are not in them): every rank runs the same extra steps
+        ktimes = kernel_profile(tr, step)
+        dp_report = dp_profile(tr, step) if dp else None
     if rank != 0:
         if dp:
             import torch.distributed as dist
             dist.destroy_process_group()
         return
     value = B * world * args.steps / dt
-    kr = kernel_rooflines(tr, ktimes, args.traffic_json)
-    if dp:   # the sharded Adam: this rank's 1/world shard of every bucket, per step
-        ev = dp_report.pop('_adam')
-        kr.append(ev)
-        kr.sort(key=lambda r: -r['avg_us'])
-    roof = dict(kr[0]) if kr else {'bound': 'hbm', 'achieved': None, 'peak': HBM_PEAK_GBS, 'unit': 'GB/s',
-                                   'frac': None, 'traffic': None}
-    roof['measured'] = ('the step\'s longest kernel with a stated algorithmic cost; its average duration from '
-                        'HIP events on its stream around the kernels of eager steps queued behind whole-step '
-                        'graph replays, after the timed region (bench.kernel_profile); the timed region '
-                        'replays graphs only')
-    roof['others'] = [{k: r[k] for k in ('tick', 'kernel', 'bound', 'achieved', 'unit', 'frac', 'avg_us', 'traffic')}
-                      for r in kr[1:]]
     out = {
         'metric': 'training cubes/sec at |V|~22k d=256; top-N recommend p50 latency',
         'value': value, 'unit': 'cubes/s', 'n_gpus': world, 'steps': args.steps,
@@ -605,18 +664,11 @@ def main():
                                                   if args.force_dp and world == 1 else ''),
                    'graph_steps': tr.multi_n if not dp else 1,
                    'prespin_ms': args.prespin_ms, 'prespin_kind': args.prespin_kind},
-        'roofline': roof,
-        'step_roofline': step_roofline(tr, dt / args.steps * 1e3, ktimes),
-        'kernel_us': ktimes,
         'final_loss': losses,
         'setup_s': setup_s,
     }
-    if dp:
-        out['dp'] = dp_report
-    if not args.no_recommend and world == 1:
-        out['recommend'] = recommend_latency()
-    if not args.no_cpu_baseline and world == 1:
-        out['cpu_baseline'] = cpu_baseline(args)
+    if args.full:
+        full_report(out, args, tr, ktimes, dp_report, world)
     print(json.dumps(out), flush=True)
     if dp:
         import torch.distributed as dist

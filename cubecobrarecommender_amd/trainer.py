@@ -18,6 +18,17 @@ from . import _lib as L
 from .layout import Layout
 
 
+def _capture(g):
+    """torch.cuda.graph(g) for this process's launching thread.  With a process group up, the
+    capture is thread-local: the collective backend's watchdog thread polls the events of earlier
+    eager collectives (an event query), which a global-mode capture on another thread forbids — the
+    query fails, the capture is invalidated and the watchdog ends the process.  Thread-local mode
+    checks the capturing thread's own calls exactly as before and leaves other threads alone."""
+    import torch.distributed as dist
+    pg = dist.is_available() and dist.is_initialized()
+    return torch.cuda.graph(g, capture_error_mode='thread_local' if pg else 'global')
+
+
 @dataclass
 class TrainConfig:
     V: int
@@ -1519,18 +1530,18 @@ class Trainer:
         g_fb, g_adam, g_rest = torch.cuda.CUDAGraph(), torch.cuda.CUDAGraph(), torch.cuda.CUDAGraph()
         if self.dp:   # (forward_backward_a | forward_backward_b | counters): the
             self.noise_ready = False           # sharded optimizer's collectives run between them
-            with torch.cuda.graph(g_fb):       # (F inside: the first step after a capture)
+            with _capture(g_fb):       # (F inside: the first step after a capture)
                 self.forward_backward_a()
-            with torch.cuda.graph(g_adam):
+            with _capture(g_adam):
                 self.forward_backward_b()
         else:
             self.noise_ready = False
-            with torch.cuda.graph(g_fb):       # F inside
+            with _capture(g_fb):       # F inside
                 self.forward_backward()
-            with torch.cuda.graph(g_adam):     # (with prefetch: + the next step's F)
+            with _capture(g_adam):     # (with prefetch: + the next step's F)
                 self.apply_adam()
         g_main = g_all = None
-        with torch.cuda.graph(g_rest):
+        with _capture(g_rest):
             self.apply_rest()
         self.g_dp = self.g_dp_nocomm = None
         if self.dp and self.cfg.dp_graph and self._sharded().nccl:
@@ -1538,11 +1549,11 @@ class Trainer:
         if not self.dp:   # rest of step k + forward/backward of step k+1 (+ its Adam)
             g_main, g_all = torch.cuda.CUDAGraph(), torch.cuda.CUDAGraph()
             self.noise_ready = self.prefetch   # F already drawn by step k's Adam launch
-            with torch.cuda.graph(g_main):
+            with _capture(g_main):
                 self.apply_rest(defer=True)
                 self.forward_backward()
             self.noise_ready = self.prefetch
-            with torch.cuda.graph(g_all):
+            with _capture(g_all):
                 self.apply_rest(defer=True)
                 self.forward_backward()
                 self.apply_adam()
@@ -1551,7 +1562,7 @@ class Trainer:
             m = self.cfg.graph_steps                    # graphs of its halves, for remainders)
             while m > 1:
                 g = torch.cuda.CUDAGraph()
-                with torch.cuda.graph(g):
+                with _capture(g):
                     for _ in range(m):
                         self.noise_ready = self.prefetch
                         self.apply_rest(defer=True)
@@ -1589,7 +1600,7 @@ class Trainer:
             self.noise_ready = self.prefetch_dp
             sh.no_comm = no_comm
             try:
-                with torch.cuda.graph(g):
+                with _capture(g):
                     self._dp_call(None, False)
             except Exception as e:   # never a silent fallback: the caller picks the parts path itself
                 raise RuntimeError(

@@ -139,3 +139,60 @@ def test_bench_rank_argv_passes_torchrun_parser(monkeypatch):
         get_args_parser().parse_args(['--nnodes=1', 'bench.py', *argv])
     monkeypatch.setattr(sys, 'argv', ['bench.py', *out])
     assert bench.parse().d == 512
+
+
+def test_bench_plain_and_full_options(monkeypatch):
+    """A plain bench.py run measures the headline only; --full and --dump-outputs are opt-in."""
+    import sys
+
+    import bench
+    monkeypatch.setattr(sys, 'argv', ['bench.py', '--gpus', '1', '--steps', '20', '--warmup', '5'])
+    a = bench.parse()
+    assert (a.steps, a.warmup, a.full, a.dump_outputs) == (20, 5, False, None)
+    monkeypatch.setattr(sys, 'argv', ['bench.py', '--full', '--dump-outputs', 'out', '--d', '512'])
+    a = bench.parse()
+    assert a.full and a.dump_outputs == 'out' and a.d == 512
+
+
+def test_bench_dump_outputs_fixed_sample_within_budget(tmp_path, monkeypatch):
+    """bench.dump_outputs: the trained tensors and the losses as float32 / float64 .npy files; an
+    output over the byte budget is written as the same seeded sample on every run; without the
+    regulariser the untrained decoder_for_reg tensors are left out."""
+    import bench
+    monkeypatch.setattr(bench.torch.cuda, 'synchronize', lambda: None)
+    monkeypatch.setattr(bench, 'DUMP_BUDGET_BYTES', 1 << 16)
+    rng = np.random.default_rng(1)
+    params = {'encoder/encoded_1/kernel': rng.standard_normal((200, 200)).astype(np.float32),
+              'encoder/encoded_1/bias': rng.standard_normal(200).astype(np.float32),
+              'decoder_for_reg/reconstruct/kernel': np.zeros((8, 8), np.float32)}
+
+    class Tr:
+        use_reg = False
+        flushed = 0
+
+        def flush(self):
+            self.flushed += 1
+
+        def params_dict(self):
+            return params
+
+        def losses(self):
+            return {'bce': 0.25, 'kl': 0.0, 'loss': 0.25}
+
+    tr = Tr()
+    bench.dump_outputs(tr, str(tmp_path / 'a'), write=True)
+    bench.dump_outputs(tr, str(tmp_path / 'b'), write=True)
+    bench.dump_outputs(tr, str(tmp_path / 'c'), write=False)     # the other ranks: flush only
+    assert tr.flushed == 3 and not (tmp_path / 'c').exists()
+    names = sorted(p.name for p in (tmp_path / 'a').iterdir())
+    assert names == ['encoder.encoded_1.bias.npy', 'encoder.encoded_1.kernel.npy', 'losses.npy']
+    got = {n: np.load(tmp_path / 'a' / n) for n in names}
+    for n in names:
+        assert np.array_equal(got[n], np.load(tmp_path / 'b' / n))
+    assert got['losses.npy'].dtype == np.float64 and got['losses.npy'].tolist() == [0.25, 0.0, 0.25]
+    assert np.array_equal(got['encoder.encoded_1.bias.npy'], params['encoder/encoded_1/bias'])
+    k = got['encoder.encoded_1.kernel.npy']
+    frac = (1 << 16) / (40000 * 4 + 200 * 4)
+    assert k.dtype == np.float32 and k.shape == (int(40000 * frac),)
+    assert sum(v.nbytes for v in got.values()) <= (1 << 16) + 200 * 4 + 24
+    assert np.isin(k, params['encoder/encoded_1/kernel']).all()

@@ -33,21 +33,21 @@ for st in "$@"; do
       eval "timeout -k 10 1000 python -u -m pytest ${arg:-tests} -m gpu -x -v --timeout 300 --timeout-method thread" \
         > "$O/tests_$i.log" 2>&1; rc=$?; tail -3 "$O/tests_$i.log"; [ $rc -ne 0 ] && { grep -E "FAIL|Error|error" "$O/tests_$i.log" | tail -20; exit $rc; } ;;
     bench)
-      timeout -k 10 400 python -u bench.py --no-cpu-baseline --no-recommend $arg > "$O/bench_$i.log" 2>&1 \
+      timeout -k 10 400 python -u bench.py --full --no-cpu-baseline --no-recommend $arg > "$O/bench_$i.log" 2>&1 \
         || { tail -30 "$O/bench_$i.log"; exit 1; }
       summ "$O/bench_$i.log" ;;
     fullbench)
-      timeout -k 10 400 python -u bench.py $arg > "$O/bench_$i.log" 2>&1 || { tail -30 "$O/bench_$i.log"; exit 1; }
+      timeout -k 10 400 python -u bench.py --full $arg > "$O/bench_$i.log" 2>&1 || { tail -30 "$O/bench_$i.log"; exit 1; }
       summ "$O/bench_$i.log" ;;
     prof)
       ( export TMPDIR=/tmp; cd /tmp && timeout -k 10 400 rocprofv3 --kernel-trace --stats --output-format csv -d "$O/prof_$i" -o run -- \
-        python3 "$R/bench.py" --no-cpu-baseline --no-recommend $arg > "$O/prof_$i.log" 2>&1 ) \
+        python3 "$R/bench.py" --full --no-cpu-baseline --no-recommend $arg > "$O/prof_$i.log" 2>&1 ) \
         || { tail -30 "$O/prof_$i.log"; exit 1; }
       summ "$O/prof_$i.log" ;;
     pmc)
       c=${arg%%:*}; a=${arg#*:}; [ "$a" == "$arg" ] && a=""
       ( export TMPDIR=/tmp; cd /tmp && timeout -s KILL 150 rocprofv3 --pmc ${c//,/ } -d "$O/pmc_$i" -o run -- \
-        python3 "$R/bench.py" --steps 16 --warmup 4 --no-cpu-baseline --no-recommend $a > "$O/pmc_$i.log" 2>&1 ) \
+        python3 "$R/bench.py" --full --steps 16 --warmup 4 --no-cpu-baseline --no-recommend $a > "$O/pmc_$i.log" 2>&1 ) \
         || { tail -30 "$O/pmc_$i.log"; exit 1; }
       python tools/prof_collect.py pmc "$O/pmc_$i" "$O/pmc_$i.json" && echo "pmc $c ok" ;;
     pmcx)
