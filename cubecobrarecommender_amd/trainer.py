@@ -8,6 +8,8 @@ activations in the GEMM operand dtype (bf16 or fp32), fp32 master weights + Adam
 flat buffer (cubecobrarecommender_amd.layout), a bf16 shadow of the weights for the MFMA path.
 torch is used only to own device memory and the stream; every computation is a HIP kernel.
 """
+import contextlib
+import gc
 from dataclasses import dataclass
 
 
@@ -18,15 +20,33 @@ from . import _lib as L
 from .layout import Layout
 
 
+@contextlib.contextmanager
 def _capture(g):
     """torch.cuda.graph(g) for this process's launching thread.  With a process group up, the
     capture is thread-local: the collective backend's watchdog thread polls the events of earlier
     eager collectives (an event query), which a global-mode capture on another thread forbids — the
     query fails, the capture is invalidated and the watchdog ends the process.  Thread-local mode
-    checks the capturing thread's own calls exactly as before and leaves other threads alone."""
+    checks the capturing thread's own calls exactly as before and leaves other threads alone.
+
+    Python's cycle collector stays off while the stream captures.  A collection that fires inside a
+    capture finalises whatever dead cycle it finds — an earlier Trainer with its graphs, memory
+    pools, tensors and events — and those finalisers make HIP calls no capture allows; the GPU
+    suite aborted (SIGABRT) inside such a collection, in the capture of a second fit()
+    (tests/test_gpu_api.py::test_fit_twice_resumes_optimizer), or not, with the allocation count
+    at which the collector happened to run.  torch.cuda.graph used to collect before every capture;
+    torch 2.10 does not unless torch.compiler.config.force_cudagraph_gc is set, so the collection
+    runs here, before the capture begins, and automatic collection resumes after it ends."""
     import torch.distributed as dist
     pg = dist.is_available() and dist.is_initialized()
-    return torch.cuda.graph(g, capture_error_mode='thread_local' if pg else 'global')
+    gc.collect()
+    was_enabled = gc.isenabled()
+    gc.disable()
+    try:
+        with torch.cuda.graph(g, capture_error_mode='thread_local' if pg else 'global'):
+            yield
+    finally:
+        if was_enabled:
+            gc.enable()
 
 
 @dataclass

@@ -518,7 +518,8 @@ int cc_dec_softmax_kl_q(const float *Z2, int32_t B, int32_t V, const float *y_re
  * no fp32 logits in HBM (model.py:64/98, train.py:85; TF 2.5 clip semantics).  Row r of the
  * regulariser rows is row row0 + r of the packed D3 images D3p ([R/32][d/16][64][8], act6p) and
  * D3tp ([d/32][ldt/16][64][8], act6tp); Wo [d][V] bf16 is read in place; Mt + card * V is the
- * M~ row of card reg_idx[r] (-1: padding row, contributes nothing); tsum[2 card], tsum[2 card + 1]
+ * M~ row of card reg_idx[r] (-1: padding row, contributes nothing to gW, gb or the loss, and its
+ * dZ row is written as zeros: the caller need not clear it); tsum[2 card], tsum[2 card + 1]
  * = sum_j t, sum_j t ln t over t = clip(M~[card, j], 1e-7, 1) (cc_kl_tsum), indexed like Mt.
  * Outputs: dZ [rows][V] bf16 (= scale * ([p >= 1e-7](-t) + p * sum_{p>=1e-7} t), for the dX
  * product), gW [d][V], gb [V], loss_partials (cc_dec_kl_blocks(V) doubles) and, with ticket,

@@ -30,6 +30,20 @@ def rel_err(a, b):
     return float(np.linalg.norm(a - b) / max(np.linalg.norm(b), 1e-30))
 
 
+def _softmax_kl_ref(Z, T, reg, B):
+    """fp64 statement of the KL term: loss rows and dZ = reg/B p (g - <p,g>)."""
+    Z = Z.astype(np.float64)
+    p = np.exp(Z - Z.max(1, keepdims=True))
+    p /= p.sum(1, keepdims=True)
+    t = np.clip(T.astype(np.float64), 1e-7, 1.0)
+    q = np.clip(p, 1e-7, 1.0)
+    kl = (t * np.log(t / q)).sum(1)
+    live = p >= 1e-7
+    S = (t * live).sum(1, keepdims=True)
+    dz = reg / B * (np.where(live, -t, 0.0) + p * S)
+    return kl, dz
+
+
 def progress(msg):
     """A progress line for multi-process GPU tests: printed (pytest shows a failing test's captured
     output) and appended to progress.log beside $CCREC_PARITY_LOG (if set), so a stuck child leaves

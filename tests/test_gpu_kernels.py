@@ -7,7 +7,7 @@ import torch
 
 from cubecobrarecommender_amd import _lib as L
 from oracle import noise_ref
-from tests.gpu_helpers import problem, rel_err
+from tests.gpu_helpers import _softmax_kl_ref, problem, rel_err
 
 pytestmark = pytest.mark.gpu
 
@@ -369,20 +369,6 @@ def test_gemm_pair_equals_two_launches(B, d, V, splits):
         assert torch.equal(a, b)
     ref = (D3t.float() @ dZt.float().t())
     assert rel_err(outs[1][1].numpy(), ref.cpu().numpy()) < 1e-5
-
-
-def _softmax_kl_ref(Z, T, reg, B):
-    """fp64 statement of the KL term: loss rows and dZ = reg/B p (g - <p,g>)."""
-    Z = Z.astype(np.float64)
-    p = np.exp(Z - Z.max(1, keepdims=True))
-    p /= p.sum(1, keepdims=True)
-    t = np.clip(T.astype(np.float64), 1e-7, 1.0)
-    q = np.clip(p, 1e-7, 1.0)
-    kl = (t * np.log(t / q)).sum(1)
-    live = p >= 1e-7
-    S = (t * live).sum(1, keepdims=True)
-    dz = reg / B * (np.where(live, -t, 0.0) + p * S)
-    return kl, dz
 
 
 @pytest.mark.parametrize('V', [701, 2500, 22000, 33000])

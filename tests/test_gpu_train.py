@@ -589,6 +589,48 @@ def test_metric_counts_exact_after_capture():
     assert 0.0 <= m['output_1_accuracy'] <= 1.0 and 0.0 <= m['output_2_accuracy'] <= 1.0
 
 
+def test_capture_keeps_the_cycle_collector_out():
+    """trainer._capture: dead cycles are collected before the capture begins and Python's cycle
+    collector stays off until it ends (a collection inside a capture finalises GPU objects with
+    HIP calls no capture allows); the collector's state is restored afterwards, also on an error."""
+    import gc
+    import weakref
+    from cubecobrarecommender_amd.trainer import _capture
+
+    class Node:
+        pass
+
+    a = Node()
+    a.me = a                          # a dead cycle once `a` is gone
+    dead = weakref.ref(a)
+    del a
+    x = torch.zeros(64, device='cuda')
+    x += 1                            # (the add kernel's module loads outside any capture)
+    x.zero_()
+    torch.cuda.synchronize()
+    g = torch.cuda.CUDAGraph()
+    assert gc.isenabled()
+    with _capture(g):
+        assert dead() is None and not gc.isenabled()
+        x += 1
+    assert gc.isenabled()
+    g.replay()
+    torch.cuda.synchronize()
+    assert x.sum().item() == 64
+    with pytest.raises(ZeroDivisionError):
+        with _capture(torch.cuda.CUDAGraph()):
+            x += 1
+            1 / 0
+    assert gc.isenabled()
+    gc.disable()                      # a caller that runs with the collector off keeps it off
+    try:
+        with _capture(torch.cuda.CUDAGraph()):
+            x += 1
+        assert not gc.isenabled()
+    finally:
+        gc.enable()
+
+
 def test_sigmoid_cat_accuracy_tie_rules():
     """cc_sigmoid_cat_accuracy's claimed tie rules (ccrec.h; parity against TF's Eigen sigmoid is
     unpinned below the saturation point): logits past 15.7243833541870117 saturate to
