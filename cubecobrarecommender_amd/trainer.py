@@ -17,7 +17,8 @@ import numpy as np
 import torch
 
 from . import _lib as L
-from .layout import Layout
+from .plan import (StepPlan, _cdf, branches_of, dx_splitk_fits, full_rows, fused_reg_fits,  # noqa: F401
+                   owner_capacity, plan_step, reg_row_shards, reg_rows_for)   # (importable from here as before)
 
 
 @contextlib.contextmanager
@@ -79,12 +80,8 @@ class TrainConfig:
     wo_tower_frac: float = -1.0    # ... on this trailing fraction of each; the rest stays in the Adam + F
     #                                launch (< 0: measured per mode — 0.6 BCE only, 0.55 with the
     #                                sampled regulariser; bench.py --wo-tower-frac sweeps)
-    dx_splits: int = 0             # decoder dX K-splits (0: measured default, 32 bf16 / 16 fp8)
-    dx_splits_reg: int = 0         # ... of the full-mode regulariser branch (0: 4)
     dx_packed_wo: bool = True      # full-mode regulariser dX from Wo's fragment image (cc_gemm_dx_splitk_pk)
     dp_defer_out: bool = True      # data parallel: the output layers' all-gather at the next step's head
-    mx8_bce_q: bool = True         # fp8: the BCE product writes dZ's MX-FP8 images (else quantiser launches)
-    mx8_pair_reg_logits: bool = True   # fp8: the regulariser logits as extra blocks of the BCE product's launch
     graph_steps: int = 8           # one process: consecutive steady-state steps per hipGraph replay (step_many)
     force_dp: bool = False         # one process driving the data-parallel step (a 1-rank process group:
     #                                zero.py's collectives on device tensors; tests and the per-rank DP profile)
@@ -105,68 +102,6 @@ class TrainConfig:
     reg_mode: str = 'sampled'      # 'sampled': B reg rows per step drawn ∝ neg_sampler (generator.py:47-51);
     #                                'full': all |V| identity rows every step, KL(M~, D2(E(I))) as the
     #                                reference README states the objective (README.md:27)
-
-
-def reg_row_shards(cdf, world):
-    """Row shards of M~ for the sampled regulariser (owner computes): boundaries
-    b[0..world] at equal cumulative neg_sampler mass — shard r = cards whose CDF value lies in
-    (r/world, (r+1)/world] — and each shard's mass m_r = cdf[b_{r+1}-1] - cdf[b_r-1].  Rank r holds
-    rows [b_r, b_{r+1}) of M~ only; every rank draws the step's world*B global reg rows (the same
-    draws one process of batch world*B makes) and computes the KL terms of the rows it owns
-    (cc_reg_rows), so the summed gradient is exactly the one-process gradient; equal mass balances
-    the expected rows per rank."""
-    cdf = np.asarray(cdf, np.float64)
-    V = len(cdf)
-    b = np.searchsorted(cdf, np.arange(world + 1) / float(world), side='right')
-    b[0], b[world] = 0, V
-    b = np.maximum.accumulate(np.minimum(b, V))
-    lo_mass = np.where(b[:-1] > 0, cdf[np.maximum(b[:-1] - 1, 0)], 0.0)
-    hi_mass = np.where(b[1:] > 0, cdf[np.maximum(b[1:] - 1, 0)], 0.0)
-    mass = hi_mass - lo_mass
-    if np.any(b[1:] <= b[:-1]) or np.any(mass <= 0):
-        raise ValueError(f'reg_row_shards: a shard of {world} is empty (one card holds > 1/{world} '
-                         'of the neg_sampler mass); use the replicated M~ (reg_shard=False)')
-    return b.astype(np.int64), mass
-
-
-def owner_capacity(mass, B, world, align=32, sigmas=6.0):
-    """Reg rows each rank reserves under owner computes: the world*B global draws land in shard r
-    Binomial(world*B, m_r) times; capacity = max over ranks of mean + 6 sigma (+1), rounded up to
-    `align` (an overflow sets the device status bit 2 and Trainer.check_status raises)."""
-    n = world * B
-    m = np.asarray(mass, np.float64)
-    need = np.max(n * m + sigmas * np.sqrt(n * m * (1.0 - m)) + 1.0)
-    return int(min(n, int(np.ceil(need / align)) * align))
-
-
-def full_rows(V, world, rank):
-    """Full mode: rank r owns identity rows [r*ceil(V/W), (r+1)*ceil(V/W)) ∩ [0, V)."""
-    per = -(-V // world)
-    return min(V, rank * per), min(V, (rank + 1) * per)
-
-
-def fused_reg_fits(hi, V, Breg):
-    """cc_dec_softmax_kl_dw's 32-bit buffer extents (decreg.hip: mt_bytes < 2^31 for M~ rows up to
-    `hi`, the Breg x V bf16 dZ < 2^32 bytes)."""
-    return hi * V * 4 <= 0x7FFFFFFF and Breg * V * 2 <= 0xFFFFFFFF
-
-
-def dx_splitk_fits(M, V, d):
-    """cc_gemm_dx_splitk's operand extents (dxgemm.hip: M*V and d*V bf16 elements < 2 GB)."""
-    return M * V * 2 < (1 << 31) and d * V * 2 < (1 << 31)
-
-
-def _cdf(neg_sampler):
-    cdf = np.cumsum(np.asarray(neg_sampler, np.float64))
-    return cdf / cdf[-1]
-
-
-def reg_rows_for(neg_sampler, world, rank, reg_mode='sampled'):
-    """Rank's M~ row shard [lo, hi): equal neg_sampler mass (sampled) or equal rows (full)."""
-    if reg_mode == 'full':
-        return full_rows(len(neg_sampler), world, rank)
-    b, _ = reg_row_shards(_cdf(neg_sampler), world)
-    return int(b[rank]), int(b[rank + 1])
 
 
 class DeviceDataset:
@@ -220,10 +155,6 @@ class DeviceDataset:
             self.reg_rows = (int(lo), int(hi))
 
 
-def branches_of(use_reg):
-    return ('decoder', 'decoder_for_reg') if use_reg else ('decoder',)
-
-
 def _neg_sampler(y_mtx):
     """generator.py:30: neg_sampler = M~.sum(0) / M~.sum() (float64)."""
     if torch.is_tensor(y_mtx):
@@ -234,94 +165,69 @@ def _neg_sampler(y_mtx):
 
 
 class Trainer:
+    # the plan's fields the step methods, zero.py, bench.py, the tools and the tests read as
+    # attributes of the same name (the has_* fields show as `buffer is not None`)
+    _PLAN_ATTRS = ('layout', 'std_layout', 'dp', 'use_reg', 'full_reg', 'owner', 'reg_rows', 'Breg', 'R', 'RP',
+                   'kl_row_scale', 'kl_loss_scale', 'mx8', 'dtype', 'fused_tower', 'reg_by_index', 'xt_rows',
+                   'embed_mfma', 'tsplits', 'dx_glds', 'fused_out', 'dz1_ld', 'fused_reg', 'd3q_in_tower',
+                   'mx8_bce_q', 'reg_logits_paired', 'splits', 'splits_reg', 'prefetch', 'prefetch_dp',
+                   'xt_in_gather', 'xt_in_tower', 'adam_packs', 'w1_off', 'fuse_w1', 'wo_range', 'f_in_tower',
+                   'early_reg_out')
+
     def __init__(self, cfg: TrainConfig, data: DeviceDataset, params_flat=None, device='cuda'):
         L.lib()  # fail loudly before allocating anything
         self.cfg, self.data = cfg, data
-        V, d, B = cfg.V, cfg.d, cfg.batch_size
-        assert data.V == V, 'dataset V mismatch'
-        assert d % 64 == 0 and (d // 64) & (d // 64 - 1) == 0, 'd must be 64 * 2^k'
-        self.dev = torch.device(device)
-        # data-parallel: gradient buckets aligned to world*64 so every rank owns an equal shard
-        self.std_layout = Layout(V, d)
-        self.dp = cfg.world > 1 or cfg.force_dp    # zero.py's sharded step (buckets, collectives)
-        # (with a bf16 shadow the biases are grouped so zero.py all-gathers the kernels' bf16 shadow)
-        self.layout = (Layout(V, d, align=cfg.world * 64, group_biases=cfg.dtype in ('bf16', 'fp8'),
-                              w1_chunks=(1 if cfg.reg_mode == 'full' else cfg.w1_chunks if cfg.w1_chunks > 0
-                                         else 1 if d <= 512 else 2))
-                       if self.dp else self.std_layout)
-        self.use_reg = cfg.reg > 0
-        if self.use_reg and data.y_reg is None:
-            raise ValueError('reg > 0 needs the M~ matrix on the device')
-        if cfg.reg_mode not in ('sampled', 'full'):
-            raise ValueError(f"reg_mode {cfg.reg_mode!r}: 'sampled' or 'full'")
-        W = cfg.world
-        self.full_reg = self.use_reg and cfg.reg_mode == 'full'
-        self.owner = self.use_reg and not self.full_reg and cfg.reg_shard and self.dp
-        ralign = 128 if cfg.dtype == 'fp8' else 32
-        # regulariser rows of this rank: rows [B, B + Breg) of every row-indexed buffer.
-        #   sampled: B draws per step (slot b of cube b), dz weight reg/B;
-        #   owner (data parallel, M~ row-sharded): the world*B global draws that fall in this
-        #     rank's shard, padded to a static capacity, masked rows reg_idx = -1; weight reg/B
-        #     (the zero.py average over ranks makes it reg/(world*B) per global row);
-        #   full: identity rows [lo, hi) (all of V on one GPU), weight reg*world/V.
-        self.reg_rows = (0, V)
-        self.Breg = B if self.use_reg else 0
-        self.kl_row_scale, self.kl_loss_scale = cfg.reg / B, 1.0 / B
+        assert data.V == cfg.V, 'dataset V mismatch'
+        # ---- 1. which path every part of the step takes (plan.py; raises for a config it rejects)
+        plan = self.plan = plan_step(cfg, cdf=data.cdf_host, data_reg_rows=data.reg_rows)
+        for k in self._PLAN_ATTRS:
+            setattr(self, k, getattr(plan, k))
+        self.wo_ranges = list(plan.wo_ranges) if plan.wo_ranges else None
+        self.rest_ranges = list(plan.rest_ranges) if plan.rest_ranges else None
+        # ---- 2. one allocation pass over what the plan names
+        self._alloc(params_flat, torch.device(device))
+        # ---- 3. the initial launches: bf16 shadow, tower / decoder operand images, M~ row sums
+        self.refresh_shadow()
+        if self.fused_reg:
+            lo, hi = self.reg_rows
+            L.call('cc_kl_tsum', L.ptr(data.y_reg), hi - lo, cfg.V, L.ptr(self.tsum), L.stream_ptr())
         if self.full_reg:
-            self.reg_rows = full_rows(V, W, cfg.rank)
-            n = self.reg_rows[1] - self.reg_rows[0]
-            self.Breg = -(-n // ralign) * ralign
-            self.kl_row_scale, self.kl_loss_scale = cfg.reg * W / V, W / V
-        elif self.owner:
-            bnd, mass = reg_row_shards(data.cdf_host, W)
-            self.reg_rows = (int(bnd[cfg.rank]), int(bnd[cfg.rank + 1]))
-            self.Breg = owner_capacity(mass, B, W, align=ralign)
-        self.R = B + self.Breg
-        # the sampled reg rows by index in the W1 gradient (cc_embed_grad_cs_reg; its column-slice
-        # path runs exactly when the fused towers and the MFMA W1 gradient do: bf16 / fp8, d % 128)
-        # (not with f_in_tower: the next step's F, drawn in the tower backward launch, rewrites the reg
-        # cards before the W1 gradient reads them; the bit matrix is not rewritten by F)
-        self.reg_by_index = bool(cfg.reg_by_index and self.use_reg and not self.full_reg
-                                 and cfg.dtype in ('bf16', 'fp8') and cfg.fused_tower and B % 32 == 0
-                                 and d <= 1024 and d % 128 == 0 and 0 < self.Breg <= 512 and not cfg.f_in_tower)
-        # rows of the MFMA W1-gradient product (its bit matrix): the cubes only when the regulariser
-        # rows enter by index (full mode: cc_embed_identity_add; sampled: cc_embed_grad_cs_reg)
-        self.xt_rows = B if (self.full_reg or self.reg_by_index) else self.R
-        self.reg_weight = 1.0
-        if self.use_reg and data.reg_rows != self.reg_rows:
-            if data.reg_rows != (0, V):
-                raise ValueError(f'dataset holds M~ rows {data.reg_rows}, rank needs {self.reg_rows}')
+            self._init_full_rows()
+        if self.t_argmax is not None:   # argmax of every resident M~ row (y_true), once
+            lo, hi = self.reg_rows
+            L.call('cc_row_argmax', L.ptr(data.y_reg), cfg.V, hi - lo, cfg.V, L.ptr(self.t_argmax), L.stream_ptr())
+
+    def _alloc(self, params_flat, dev):
+        """2. every buffer the plan's paths need, and the step's host-side state."""
+        cfg, data, plan = self.cfg, self.data, self.plan
+        V, d, B, R = cfg.V, cfg.d, cfg.batch_size, self.R
+        self.dev = dev
+        if self.use_reg and data.reg_rows != self.reg_rows:   # the dataset holds all of M~: keep this rank's rows
             lo, hi = self.reg_rows
             data.y_reg, data.reg_rows = data.y_reg[lo:hi].contiguous(), self.reg_rows
-        if cfg.dtype not in ('bf16', 'fp32', 'fp8'):
-            raise ValueError(f'dtype {cfg.dtype!r}: bf16, fp32 or fp8')
-        self.mx8 = cfg.dtype == 'fp8'
-        self.dtype = L.CC_F32 if cfg.dtype == 'fp32' else L.CC_BF16
         self.tdt = torch.float32 if cfg.dtype == 'fp32' else torch.bfloat16
-        if self.mx8 and (d % 128 or self.R % 128 or B % 32):
-            raise ValueError('fp8 (MX) decoder GEMMs need d and the row count (B, 2B with reg) multiples of 128')
         P = self.layout.total
-        f32 = dict(device=self.dev, dtype=torch.float32)
+        f32 = dict(device=dev, dtype=torch.float32)
+        i32 = dict(device=dev, dtype=torch.int32)
+        f64 = dict(device=dev, dtype=torch.float64)
+        T = dict(device=dev, dtype=self.tdt)
         self.params = torch.zeros(P, **f32)
         if params_flat is not None:   # given in the standard (cc_param_layout) layout
             self.load_standard(self.params, params_flat)
         self.m = torch.zeros(P, **f32)
         self.v = torch.zeros(P, **f32)
         self.grads = torch.zeros(P, **f32)
-        self.shadow = torch.zeros(P, device=self.dev, dtype=torch.bfloat16) if self.dtype == L.CC_BF16 else None
-        self.refresh_shadow()
-        self.state = torch.zeros(4, device=self.dev, dtype=torch.int64)   # {step, batch, epoch, ticket}
-        self.tickets = torch.zeros(4, device=self.dev, dtype=torch.int32)  # last-block hand-offs
+        self.shadow = torch.zeros(P, device=dev, dtype=torch.bfloat16) if self.dtype == L.CC_BF16 else None
+        self.state = torch.zeros(4, device=dev, dtype=torch.int64)   # {step, batch, epoch, ticket}
+        self.tickets = torch.zeros(4, **i32)                         # last-block hand-offs
         self.x_cap = max(1, data.max_n + int(data.max_n * 0.8) + 1)
-        R, VW, XW = self.R, (V + 31) // 32, (self.xt_rows + 31) // 32
-        i32 = dict(device=self.dev, dtype=torch.int32)
+        VW, XW = (V + 31) // 32, (self.xt_rows + 31) // 32
         self.x_cnt = torch.zeros(R, **i32)
         self.x_idx = torch.zeros(R, self.x_cap, **i32)
         self.y_bits = torch.zeros(B, VW, **i32)
         self.xt_bits = torch.zeros(V, XW, **i32)
         self.reg_idx = torch.zeros(max(self.Breg, 1), **i32)
         self.status = torch.zeros(1, **i32)
-        T = dict(device=self.dev, dtype=self.tdt)
         self.H1 = torch.zeros(R, d, **T)
         self.H2 = torch.zeros(R, 256, **T)
         self.H3 = torch.zeros(R, 128, **T)
@@ -337,50 +243,19 @@ class Trainer:
         self.gH3 = torch.zeros(R, 128, **T)
         self.gH2 = torch.zeros(R, 256, **T)
         self.gPre1 = torch.zeros(R, d, **f32)
-        self.Z2 = None             # materialised fp32 D2 logits (the unfused regulariser path only)
-        self.splits = max(1, min(cfg.dx_splits or (16 if cfg.dtype == 'fp8' else 32), V // 512))   # decoder dX: K = V (fp8: 256 x 256 tiles, 16 splits measured best)
-        # the regulariser branch's dX: M = Breg rows; with thousands of rows (full mode) the output
-        # tiles alone fill the chip — no split-K
-        # full-mode regulariser (~|V| rows): 2 K-splits (tools/micro/dx_full_micro.py at |V| = 22,000:
-        # 1 split 643 us, 2 or 4 splits 515 us, the library GEMM 391-399 us)
-        # (the 128 x 256-tile kernel of dxgemm.hip for tall M: 4 splits)
-        self.splits_reg = self.splits if self.Breg <= 1024 else (cfg.dx_splits_reg or 4)
-        self.tsplits = max(1, min(8, B // 128))             # tower dW: K = rows (B or 2B)
         self.split_buf = torch.zeros(max(self.splits * B * d, self.splits_reg * self.Breg * d,
                                          2 * self.tsplits * max(d, 256) * 256), **f32)
         self.cs_buf = torch.zeros(2 * self.tsplits * max(d, 256), **f32)
-        tiles = ((B + 63) // 64) * ((V + 63) // 64)
-        self.bce_part = torch.zeros(tiles, device=self.dev, dtype=torch.float64)
-        self.kl_part = torch.zeros(max(self.Breg, 1), device=self.dev, dtype=torch.float64)
+        self.bce_part = torch.zeros(((B + 63) // 64) * ((V + 63) // 64), **f64)
+        self.kl_part = torch.zeros(max(self.Breg, 1), **f64)
         self.id_ws = (torch.zeros(int(L.lib().cc_embed_identity_ws(self.Breg, d)) // 4 + 1, **f32)
                       if self.full_reg else None)
-        self.loss_dev = torch.zeros(2, device=self.dev, dtype=torch.float64)
-        # fused 32-row-block towers (tower.hip) when the widths fit; generic GEMMs otherwise
-        self.fused_tower = cfg.fused_tower and (B % 32 == 0) and d <= (1024 if self.dtype == L.CC_BF16 else 256)
-        # bf16 path: the W1 gradient on MFMA (cc_embed_grad_mfma) from dPre1^T bf16 [d][RP]
-        # written by the tower backward chain (columns R..RP-1 stay zero)
-        self.embed_mfma = self.dtype == L.CC_BF16 and self.fused_tower and d % 128 == 0 and self.xt_rows <= 2048
-        self.RP = (R + 63) // 64 * 64
-        # decoder dX on the LDS-DMA pipelined split-K kernel (dxgemm.hip; other dtypes: gemm.hip's)
-        self.dx_glds = self.dtype == L.CC_BF16
-        self.WoP = None   # the full-mode regulariser's Wo as its MFMA fragment image (below)
-        # D1 output layer fused (logits + BCE + dZ + dWo, csrc/decout.hip) where its shape fits
-        self.fused_out = (self.dtype == L.CC_BF16 and self.fused_tower and not self.mx8 and d in (128, 256, 512)
-                          and B in (128, 256, 512))
-        # the fused D1 kernel's dZ rows at a pitch of whole 64-element (128-B) groups: at |V| = 22,000
-        # the natural pitch (44,000 B) starts every other row mid-line, so a wave's 64-B row segments
-        # straddle lines shared with the next row / the next 96-column slice; the dX product reads
-        # dZ at the padded pitch (measured r04u: 154.0 / 154.2 -> 153.3 / 152.5 us/step, FETCH_SIZE
-        # of the kernel unchanged)
-        self.dz1_ld = V
-        self.dZ1 = None
-        if self.fused_out:
-            self.dz1_ld = -(-V // 64) * 64 if cfg.dz_pad else V
-            self.dZ1 = torch.zeros(B, self.dz1_ld, **T)
+        self.loss_dev = torch.zeros(2, **f64)
+        # the fused D1 kernel's own dZ (padded pitch), dPre1^T bf16 [d][RP] (columns R..RP-1 stay zero)
+        self.dZ1 = torch.zeros(B, self.dz1_ld, **T) if self.fused_out else None
         self.gPre1T = torch.zeros(d, self.RP, **T) if self.embed_mfma else None
-        if self.mx8 and not self.fused_tower:
-            raise ValueError('fp8 needs the fused towers (fused_tower=True, B % 32 == 0)')
         self.wpack = self.D3p = self.D3tp = self.hpt = self.gpt = self.gpre1p = self.eg_tickets = None
+        self.WoP = None
         if self.fused_tower:
             self.tower_layers = ('encoder/encoded_2', 'encoder/encoded_3', 'encoder/bottleneck',
                                  'decoder/decoded_1', 'decoder/decoded_2', 'decoder/decoded_3',
@@ -389,48 +264,33 @@ class Trainer:
             sizes = [int(np.prod(self.layout.shape(n + '/kernel'))) for n in self.tower_layers]
             self.wt_off = np.concatenate([[0], np.cumsum([(n + 63) // 64 * 64 for n in sizes])])
             self.wt = torch.zeros(int(self.wt_off[-1]), **T)
-            # fragment-packed forward/backward weight images for the bf16 tower kernels (d <= 256:
-            # fast, 256 < d <= 1024: wide; written with wt by cc_tower_transpose and by the Adam
-            # launch; the opt-in fused Adam writes only wt)
-            pack = self.dtype == L.CC_BF16 and d <= 1024
-            self.wpack = torch.zeros(2, int(self.wt_off[-1]), **T) if pack else None
-            # ... and D3 as packed operand images of the fused D1 output kernel (cc_dec_bce_dw)
-            self.D3p = torch.zeros(R * d, **T) if pack else None
-            self.D3tp = torch.zeros(d * R, **T) if pack else None
-            # ... and every tower layer's input / output-gradient as packed transposed images
-            # (the dW kernel's MFMA operands): H widths d,256,128,64,128,256; G 256,128,64,128,256,d
-            self.hpt = [torch.zeros(R * w, **T) for w in (d, 256, 128, 64, 128, 256)] if pack else None
-            self.gpt = [torch.zeros(R * w, **T) for w in (256, 128, 64, 128, 256, d)] if pack else None
-            # dPre1 as packed transposed fragments (the W1 gradient's B operand; rows past R zero)
-            self.gpre1p = (torch.zeros(d * self.RP, **T) if pack and self.embed_mfma and d == 256
-                           else None)
-            # the W1 gradient by column slices (cc_embed_grad_cs; without the MFMA operands: the row kernels):
-            # one zeroed ticket per row chunk, left zero by every call
-            self.eg_tickets = (torch.zeros(max(1, int(L.lib().cc_embed_grad_cs_tickets(V, d, self.xt_rows))),
-                                           device=self.dev, dtype=torch.int32)
-                               if (self.gpre1p is not None or self.embed_mfma)
-                               else None)
-            assert not self.reg_by_index or self.eg_tickets is not None, 'reg_by_index needs the column-slice W1 gradient'
-            slab = int(L.lib().cc_tower_slab_elems(d))
-            self.slab = torch.zeros((R // 32) * slab, **f32)
-            # D2 output layer fused (logits twice -> softmax -> KL -> dZ -> dWo, csrc/decreg.hip): bf16,
-            # d in {128, 256, 512} with the packed D3 images (the same shape class as the fused D1 kernel)
-            # (its buffer descriptors address M~ up to row hi and the Breg x V bf16 dZ with 32-bit
-            # extents: larger card pools fall back to the Z2 path instead of failing)
-            self.fused_reg = (self.use_reg and self.D3p is not None and not self.mx8 and d in (128, 256, 512)
-                              and self.Breg % 32 == 0 and fused_reg_fits(self.reg_rows[1], V, self.Breg))
+            if plan.has_wpack:
+                # fragment-packed forward/backward weight images for the bf16 tower kernels
+                # (written with wt by cc_tower_transpose and by the Adam launch; the opt-in fused
+                # Adam writes only wt)
+                self.wpack = torch.zeros(2, int(self.wt_off[-1]), **T)
+            if plan.has_D3p:   # D3 as packed operand images of the fused output kernels
+                self.D3p = torch.zeros(R * d, **T)
+                self.D3tp = torch.zeros(d * R, **T)
+            if plan.has_wpack:
+                # ... and every tower layer's input / output-gradient as packed transposed images
+                # (the dW kernel's MFMA operands): H widths d,256,128,64,128,256; G 256,128,64,128,256,d
+                self.hpt = [torch.zeros(R * w, **T) for w in (d, 256, 128, 64, 128, 256)]
+                self.gpt = [torch.zeros(R * w, **T) for w in (256, 128, 64, 128, 256, d)]
+            if plan.has_gpre1p:   # dPre1 as packed transposed fragments (the W1 gradient's B operand; rows past R zero)
+                self.gpre1p = torch.zeros(d * self.RP, **T)
+            if plan.has_w1_cs:    # the column-slice W1 gradient: one zeroed ticket per row chunk, left zero by every call
+                self.eg_tickets = torch.zeros(max(1, int(L.lib().cc_embed_grad_cs_tickets(V, d, self.xt_rows))), **i32)
+            self.slab = torch.zeros((R // 32) * int(L.lib().cc_tower_slab_elems(d)), **f32)
             # decoder operands kept k-contiguous: D3^T (tower fwd), dZ^T (BCE epilogue), Wo^T shadow
             self.D3t = torch.zeros(d, R, **T)
             self.dZt = [torch.zeros(V, n, **T) if not (k == 1 and self.fused_reg) else None
                         for k, n in enumerate(self.branch_rows())]   # [branch][V][rows]
             self.WoT = torch.zeros(len(branches_of(self.use_reg)), V, d, **T)
-            # the full-mode regulariser's dX takes Wo as its MFMA B-fragment image (cc_pack_frag_b,
-            # refreshed with the other decoder operands after each update; cc_gemm_dx_splitk_pk)
-            if (self.full_reg and self.fused_reg and self.dx_glds and d % 256 == 0 and V % 8 == 0
-                    and self.Breg % 128 == 0 and cfg.dx_packed_wo):
+            if plan.has_WoP:   # Wo as its MFMA B-fragment image (refreshed with the other decoder operands)
                 self.WoP = torch.zeros(int(L.lib().cc_pack_frag_b_size(d, V)) // 2, **T)
             if self.mx8:   # MX-FP8 operand images of the decoder output layers (csrc/mx8.hip)
-                nbr, u8 = len(branches_of(self.use_reg)), dict(device=self.dev, dtype=torch.uint8)
+                nbr, u8 = len(branches_of(self.use_reg)), dict(device=dev, dtype=torch.uint8)
                 self.Vp = (V + 127) // 128 * 128
                 self.WoT8 = torch.zeros(nbr, V, d, **u8)                  # fwd B operand [V][d]
                 self.WoT8s = torch.zeros(nbr, V, d // 32, **u8)
@@ -444,125 +304,32 @@ class Trainer:
                 self.dZqs = torch.zeros(R, self.Vp // 32, **u8)
                 self.dZtq = [torch.zeros(V, n, **u8) for n in self.branch_rows()]   # dW B operand (K = rows)
                 self.dZtqs = [torch.zeros(V, n // 32, **u8) for n in self.branch_rows()]
-            self.targs = self._tower_args()
-            # config 5 on the wide chains: the tower forward writes D3's MX-FP8 images itself (two
-            # quantiser launches less per step)
-            self.d3q_in_tower = self.mx8 and d > 256 and self.wpack is not None and R % 32 == 0
-            # the BCE product makes dZ's MX-FP8 images and the bias gradient in its epilogue
-            # (cc_gemm_mx8_bce_q: B % 32 == 0, B <= 512); mx8_bce_q=False keeps the quantiser launches
-            self.mx8_bce_q = self.mx8 and B % 32 == 0 and B <= 512 and cfg.mx8_bce_q
-            if self.d3q_in_tower:
-                t = self.targs
-                t.d3q, t.d3qs = self.D3q.data_ptr(), self.D3qs.data_ptr()
-                t.d3tq, t.d3tqs = self.D3tq.data_ptr(), self.D3tqs.data_ptr()
-            self.transpose_tower()
-        else:
-            self.targs = None
-            self.d3q_in_tower = False
-            self.mx8_bce_q = False
-        if not self.fused_tower:
-            self.fused_reg = False
-        if self.use_reg and not self.fused_reg:
-            self.Z2 = torch.zeros(self.Breg, V, **f32)
-        # config 5: the regulariser logits ride in the BCE product's launch (cc_gemm_mx8_bce_q2)
-        self.reg_logits_paired = (self.mx8_bce_q and self.use_reg and not self.fused_reg and self.fused_tower
-                                  and cfg.mx8_pair_reg_logits)
+        # materialised fp32 D2 logits (the unfused regulariser path only)
+        self.Z2 = torch.zeros(self.Breg, V, **f32) if plan.has_Z2 else None
         if self.fused_reg:
             lo, hi = self.reg_rows
             self.tsum = torch.zeros(hi - lo, 2, **f32)    # per M~ row {sum t, sum t ln t} (t clipped), once
-            L.call('cc_kl_tsum', L.ptr(data.y_reg), hi - lo, V, L.ptr(self.tsum), L.stream_ptr())
             self.kl_ws = torch.zeros(int(L.lib().cc_dec_kl_ws_size(self.Breg, V)) // 4 + 4, **f32)
             self.kl_flags = 0   # cc_dec_kl_args.flags (tests: the A/B of decreg.hip's alternative full-mode paths)
-            self.kl_part = torch.zeros(max(int(L.lib().cc_dec_kl_blocks(V)), 1), device=self.dev,
-                                       dtype=torch.float64)
-        if self.full_reg:
-            self._init_full_rows()
+            self.kl_part = torch.zeros(max(int(L.lib().cc_dec_kl_blocks(V)), 1), **f64)
         # metrics=['accuracy']: {output 1 correct rows, output 2 correct rows, output 2 rows} summed on
         # the device
-        self.acc_counts = None
+        self.acc_counts = self.t_argmax = None
         if cfg.metrics:
-            self.acc_counts = torch.zeros(3, device=self.dev, dtype=torch.int64)
+            self.acc_counts = torch.zeros(3, device=dev, dtype=torch.int64)
             self.Z1m = torch.zeros(B, V, **f32)
             if self.use_reg:
                 # (full mode's |V| identity rows go through a bounded buffer in row chunks)
                 self.Z2m = self.Z2 if self.Z2 is not None else torch.zeros(min(self.Breg, 1024), V, **f32)
-                lo, hi = self.reg_rows       # argmax of every resident M~ row (y_true), once
-                self.t_argmax = torch.zeros(hi - lo, device=self.dev, dtype=torch.int32)
-                L.call('cc_row_argmax', L.ptr(data.y_reg), V, hi - lo, V, L.ptr(self.t_argmax), L.stream_ptr())
-        # F for the next step in the Adam launch (cc_adam_noise): Adam is HBM-bound, F latency-
-        # bound; F then leaves the forward's critical path.  noise_ready: the batch buffers
-        # already hold the batch the next forward_backward consumes.
-        self.prefetch = cfg.prefetch_noise and not self.dp
-        # data parallel: F of the next step is its own launch (cc_noise_next) beside the exchange of
-        # the last gradient buckets (zero.py after_b), off the next forward's critical path
-        self.prefetch_dp = cfg.prefetch_noise and self.dp
-        # one process: F (in the Adam launch) writes its x rows as bitmasks and the next E1 gather
-        # launch bit-transposes them into the W1-gradient bitmask (cc_embed_gather_fwd_xt) — F's
-        # scattered xt atomics queued behind the Adam streams (measured: the Adam + F launch
-        # 40.5 -> 36.9 us without them; the same atomics in the gather cost it 13 us)
-        self.xt_in_gather = self.prefetch and self.dtype == L.CC_BF16
-        # (F's x rows as bitmasks [R][ceil(V/32)]; rows F does not draw stay zero)
-        self.x_bits = (torch.zeros(self.R, (cfg.V + 31) // 32, device=self.dev, dtype=torch.int32)
-                       if self.xt_in_gather else None)
-        # ... in the tower forward launch instead when its fast kernel runs (d <= 256): its 16-32
-        # chain blocks leave the other CUs idle (measured: in the gather launch the transpose
-        # blocks cost it 2-3 us)
-        self.xt_in_tower = self.xt_in_gather and self.targs is not None and cfg.d <= 256
-        if self.xt_in_tower:
-            self.targs.x_bits, self.targs.xt_bits = self.x_bits.data_ptr(), self.xt_bits.data_ptr()
-            self.targs.xt_V, self.targs.xt_rows = cfg.V, self.xt_rows
-        # the fused D1 kernel's target masks as an image in accumulator-register row order
-        # (cc_tower_args.y_img), transposed from F's y words by the tower forward launch's extra
-        # blocks: the D1 epilogue then loads a tile's 16 lane masks with two scalar loads
-        self.y_img = None
-        if (self.fused_out and self.fused_tower and self.targs is not None and self.dtype == L.CC_BF16
-                and cfg.d <= 256):
-            self.y_img = torch.zeros((cfg.V + 31) // 32 * B, device=self.dev, dtype=torch.int32)
-            self.targs.y_bits, self.targs.y_img, self.targs.y_V = self.y_bits.data_ptr(), self.y_img.data_ptr(), cfg.V
-        # one process, packed tower images: the Adam + F launch also rewrites the tower kernels'
-        # packed images and advances the step counters (cc_adam_noise_pack) — the next step
-        # starts without a counters/transposes launch
-        self.adam_packs = self.prefetch and self.wpack is not None
-        # TF Adam on W1 in the W1-gradient kernel's epilogue (cc_embed_grad_cs_adam): the main Adam
-        # launch then starts after W1 (W1 is the first tensor of the layout).  One process only
-        # (DP reduces the gradient first), the column-slice kernel, not the full-mode regulariser
-        # (its identity rows add to the W1 gradient after that kernel).
-        self.w1_off = self.layout.offset('encoder/encoded_1/bias')   # = W1's padded size
-        self.fuse_w1 = (cfg.fuse_w1_adam and self.adam_packs and self.eg_tickets is not None and not self.full_reg
-                        and self.layout.offset('encoder/encoded_1/kernel') == 0)
-        self.adam_pack = self._adam_pack_desc() if self.adam_packs else None
-        # TF Adam on the decoder output layers (Wo, bo, and with the sampled regulariser Wo_reg, bo_reg:
-        # ~96% of the parameters after W1) in extra workgroups of the tower backward launch
-        # (cc_tower_bwd_chain_adam): their gradients are final after the output-layer kernels, the dX
-        # products have read their bf16 shadows, and the 16-32 latency-bound chain blocks leave the
-        # other CUs idle.  Only their trailing wo_tower_frac: the main Adam launch (which also runs
-        # the next step's F, latency-bound too) keeps the rest to stream beside F.  wo_ranges: the
-        # tower launch's [lo, hi) flat ranges; rest_ranges: the Adam launch's (W1 end onwards).
-        self.wo_ranges, self.rest_ranges = None, None
-        if (cfg.wo_adam_in_tower and self.fuse_w1 and self.fused_out and (not self.use_reg or self.fused_reg)
-                and self.targs is not None and self.dtype == L.CC_BF16 and cfg.d <= 256):
-            frac = cfg.wo_tower_frac if cfg.wo_tower_frac >= 0 else (0.55 if self.use_reg else 0.6)
-            frac = min(max(float(frac), 0.0), 1.0)
-            lay = self.layout
-            spans = [(lay.offset('decoder/reconstruct/kernel'), lay.main_total)]
-            if self.use_reg:
-                spans.append((lay.offset('decoder_for_reg/reconstruct/kernel'), lay.total))
-            wo = [(hi - int((hi - lo) * frac) // 256 * 256, hi) for lo, hi in spans]
-            if all(a < b for a, b in wo):
-                self.wo_ranges = wo
-                rest, lo = [], self.w1_off
-                for a, b in wo:        # the complement inside [W1 end, end of the Adam range)
-                    rest.append((lo, a))
-                    lo = b
-                self.rest_ranges = rest
-        self.wo_range = self.wo_ranges[0] if self.wo_ranges else None   # (tests: is the placement on)
-        # the next step's F in the tower backward launch: one process with F prefetched (xt bits by
-        # the tower forward's transpose, so F sets none the W1 gradient still reads), the packed
-        # Adam launch, the fast bf16 chains
-        self.f_in_tower = (cfg.f_in_tower and self.adam_packs and self.xt_in_tower and self.fused_tower
-                           and self.dtype == L.CC_BF16 and cfg.d <= 256 and not self.full_reg)
+                self.t_argmax = torch.zeros(self.reg_rows[1] - self.reg_rows[0], **i32)
+        # F's x rows as bitmasks [R][ceil(V/32)] (rows F does not draw stay zero) and the fused D1
+        # kernel's target-mask image, both transposed by another launch's extra blocks
+        self.x_bits = torch.zeros(R, VW, **i32) if plan.has_x_bits else None
+        self.y_img = torch.zeros(VW * B, **i32) if plan.has_y_img else None
+        self.targs = self._tower_args() if self.fused_tower else None
+        self.adam_pack =self._adam_pack_desc() if self.adam_packs else None
         self._adv_deferred = False   # the previous step's counter advance rides in the E1 gather
-        self.noise_ready = False
+        self.noise_ready = False     # the batch buffers already hold the batch the next forward_backward consumes
         self.host_batch = False      # load_batch(): the next step runs on a host-given batch
         self.perms = None
         self.batches_per_epoch = max(1, data.C // (B * cfg.world))   # generator.py:36 (__len__)
@@ -573,12 +340,6 @@ class Trainer:
         self.sharded = None
         self.pending_rest = False    # one process: step k's counters/transposes run at the head
         #                              of step k+1's forward graph (one graph launch less per step)
-        self.side = torch.cuda.Stream(device=self.dev)   # dW / slab reduce / losses / transposes
-        # the side-stream work (output-layer dW, slab reduces) as graph branches: measured slower than
-        # keeping it on the one stream (r03: the tower dW beside the W1 gradient, 166.5 -> 181.7 us
-        # per step — every kernel of the graph got slower), so _fork / _join only mark where it could
-        # branch
-        self.overlap = False
         self.timing = False          # bench.py: HIP events around the main kernels
         self.events = {}
         # zero.py (one captured data-parallel step): called on the launching stream once the decoder
@@ -591,9 +352,6 @@ class Trainer:
         # chunk): name -> callable, fired once on the launching stream right after the bucket's
         # last kernel
         self.bucket_hooks = {}
-        # the data-parallel bf16 / fp8 layout: both output layers are one early bucket, so its
-        # exchange waits for the regulariser branch's output-layer gradient and dX too
-        self.early_reg_out = self.dp and self.layout.group_biases and self.use_reg
 
     def branch_rows(self):
         """Rows of each decoder branch: B cubes, then Breg regulariser rows."""
@@ -628,35 +386,18 @@ class Trainer:
             raise RuntimeError(f'device status {st}: ' + ('x_cap overflow ' if st & 1 else '') +
                                ('owner-computes reg capacity overflow' if st & 2 else ''))
 
-    def _tick(self, name, stream=None):
+    def _tick(self, name):
         """Record a HIP event on the launching stream (bench timing); returns a closer."""
         if not self.timing:
             return lambda: None
         e0 = torch.cuda.Event(enable_timing=True)
-        e0.record(stream)
+        e0.record()
 
         def close():
             e1 = torch.cuda.Event(enable_timing=True)
-            e1.record(stream)
+            e1.record()
             self.events.setdefault(name, []).append((e0, e1))
         return close
-
-    # ---- a second stream for work off the critical path (graph branches when captured)
-    def _fork(self):
-        """The side stream starts after everything issued so far on the current stream."""
-        if not self.overlap:
-            return L.stream_ptr(None)
-        ev = torch.cuda.Event()
-        ev.record(torch.cuda.current_stream())
-        self.side.wait_event(ev)
-        return L.stream_ptr(self.side)
-
-    def _join(self):
-        if not self.overlap:
-            return
-        ev = torch.cuda.Event()
-        ev.record(self.side)
-        torch.cuda.current_stream().wait_event(ev)
 
     def kernel_times_ms(self):
         """Average duration (ms) per instrumented kernel over the recorded launches."""
@@ -694,7 +435,7 @@ class Trainer:
             t.act6p, t.act6tp = self.D3p.data_ptr(), self.D3tp.data_ptr()
         if self.gpre1p is not None:
             t.gpre1p = self.gpre1p.data_ptr()
-        if getattr(self, 'hpt', None) is not None:
+        if self.hpt is not None:
             for a in range(6):
                 t.hpt[a], t.gpt[a] = self.hpt[a].data_ptr(), self.gpt[a].data_ptr()
         t.gD3 = self.gD3.data_ptr()
@@ -703,6 +444,14 @@ class Trainer:
         t.gpre1 = self.gPre1.data_ptr()
         t.gpre1t = self.gPre1T.data_ptr() if self.gPre1T is not None else None
         t.slab = self.slab.data_ptr()
+        if self.d3q_in_tower:   # config 5 on the wide chains: the tower forward writes D3's MX-FP8 images
+            t.d3q, t.d3qs = self.D3q.data_ptr(), self.D3qs.data_ptr()
+            t.d3tq, t.d3tqs = self.D3tq.data_ptr(), self.D3tqs.data_ptr()
+        if self.xt_in_tower:    # ... bit-transposes F's x rows into the W1-gradient bitmask
+            t.x_bits, t.xt_bits = self.x_bits.data_ptr(), self.xt_bits.data_ptr()
+            t.xt_V, t.xt_rows = self.cfg.V, self.xt_rows
+        if self.y_img is not None:   # ... and F's y words into the fused D1 kernel's mask image
+            t.y_bits, t.y_img, t.y_V = self.y_bits.data_ptr(), self.y_img.data_ptr(), self.cfg.V
         return t
 
     def _adam_pack_desc(self):
@@ -746,8 +495,7 @@ class Trainer:
         """Re-derive the bf16 shadow (and the transposed tower operands) from the fp32 master."""
         if self.shadow is not None:
             L.call('cc_to_bf16', L.ptr(self.params), L.ptr(self.shadow), self.layout.total, L.stream_ptr())
-        if getattr(self, 'targs', None) is not None:
-            self.transpose_tower()
+        self.transpose_tower()
 
     def set_epoch_permutation(self, perm):
         """Upload one epoch's cube order (generator.py:63-72) and reset the batch counter."""
@@ -843,11 +591,11 @@ class Trainer:
                            guide_log2=self.data.guide_log2, state=self.state.data_ptr(),
                            x_cnt=self.x_cnt.data_ptr(), x_idx=self.x_idx.data_ptr(),
                            y_bits=self.y_bits.data_ptr(),
-                           xt_bits=0 if getattr(self, 'xt_in_gather', False) else self.xt_bits.data_ptr(),
+                           xt_bits=0 if self.xt_in_gather else self.xt_bits.data_ptr(),
                            reg_idx=self.reg_idx.data_ptr(), status=self.status.data_ptr(),
                            xt_rows=self.xt_rows, reg_slots=B * cfg.world, reg_lo=self.reg_rows[0],
                            reg_hi=self.reg_rows[1], reg_cap=self.Breg,
-                           x_bits=self.x_bits.data_ptr() if getattr(self, 'xt_in_gather', False) else 0)
+                           x_bits=self.x_bits.data_ptr() if self.xt_in_gather else 0)
 
     def _gemm(self, M, N, K, A, lda, B, ldb, ta=0, tb=0, epi=L.CC_EPI_STORE, ldc=None, bias=None,
               relu=0, C=None, Cf=None, H=None, y_bits=None, scale=0.0, partials=None, splits=1,
@@ -950,8 +698,7 @@ class Trainer:
         self._fire('hook_d1')   # (zero.py: the output layers' deferred all-gather landed)
         t = self._tick('dec_bce_fwd')
         if self.fused_out:     # logits + BCE + dZ + dWo/dbo in one pass (csrc/decout.hip)
-            pk = (L.ptr(self.D3p) if self.D3p is not None else None,
-                  L.ptr(self.D3tp) if self.D3p is not None else None, None,
+            pk = (L.ptr(self.D3p), L.ptr(self.D3tp), None,
                   self.w('decoder/reconstruct/kernel'),   # Wo [d][V]: slices transposed in LDS
                   self.pf('decoder/reconstruct/bias'), B, d, V, L.ptr(self.y_bits))
             tail = (L.ptr(self.dZ1), self.dz1_ld, self.gp('decoder/reconstruct/kernel'),
@@ -989,7 +736,6 @@ class Trainer:
                        loss_out=L.ptr(self.loss_dev), loss_scale=1.0 / (B * V),
                        ticket=L.ptr(self.tickets))
         t()
-        ss = self._fork()          # off the critical path: loss reductions, output-layer dW
         # ---- D2 output + softmax + KL vs M~ rows (model.py:98; train.py:85)
         if self.use_reg and self.fused_reg:   # logits -> softmax -> KL -> dZ, dWo, dbo (decreg.hip)
             lo, hi = self.reg_rows
@@ -1030,16 +776,13 @@ class Trainer:
             t()
             if self.fused_tower:   # dZ2^T [V][Breg]: the k-contiguous operand of the reg branch's dW
                 L.call('cc_transpose', self.dtype, L.ptr(self.dZout[B:]), Br, V, L.ptr(self.dZt[1]), s)
-            ss = self._fork()
-            L.call('cc_reduce_loss', L.ptr(self.kl_part), Br, self.kl_loss_scale, L.ptr(self.loss_dev[1:]), ss)
+            L.call('cc_reduce_loss', L.ptr(self.kl_part), Br, self.kl_loss_scale, L.ptr(self.loss_dev[1:]), s)
         if self.acc_counts is not None:
             self._metrics_step(s)
-        # ---- backward through the output layers and decoder towers.  The output layers' dW
-        # (side stream) and dX -> towers (this stream) only share read-only inputs.
+        # ---- backward through the output layers and decoder towers
         for k, (pre, (r0, r1)) in enumerate(branches):
             if k == 1:                 # branch 0 (D1) done: its dW final, its Wo shadow read
-                if self.hook_out is not None and (not self.early_reg_out or self.fused_reg):
-                    self._join()       # (dW may have been issued on the side stream)
+                if not self.early_reg_out or self.fused_reg:
                     self._fire('hook_out')   # (fused D2: the regulariser's output layer is final too)
                 if not self.early_reg_out:
                     self._fire('hook_dx')
@@ -1074,11 +817,13 @@ class Trainer:
                 gw = self._gemm(d, V, nr, **self._dec_dw(k, r0), ta=0, tb=1,
                                 Cf=self.gp(pre + '/reconstruct/kernel'),
                                 colsum=None if self.mx8 else self.gp(pre + '/reconstruct/bias'), launch=False)
-                if not self.timing and not self.overlap:   # dX (split-K) and dW in one grouped launch
+                # dX (split-K) and dW in one grouped launch (plan.py: dW as a second stream's graph
+                # branch was measured slower); bench.py --full times them one by one
+                if not self.timing:
                     L.call('cc_gemm_pair', L.C.byref(gx), L.C.byref(gw), s)
                 else:
-                    t = self._tick('dec_dW', self.side if self.overlap else None)
-                    L.call('cc_gemm', L.C.byref(gw), ss)
+                    t = self._tick('dec_dW')
+                    L.call('cc_gemm', L.C.byref(gw), s)
                     t()
                     t = self._tick('dec_dX')
                     L.call('cc_gemm', L.C.byref(gx), s)
@@ -1086,10 +831,9 @@ class Trainer:
                 L.call('cc_splitk_reduce', self.dtype, L.ptr(self.split_buf), splits, nr, d,
                        L.ptr(self.D3[r0:]), L.ptr(self.gD3[r0:]), None, None, None, s)
                 continue
-            t = self._tick('dec_dW', self.side if self.overlap else None)
+            t = self._tick('dec_dW')
             self._gemm(d, V, nr, L.ptr(self.D3[r0:]), d, L.ptr(dz), V, ta=1, tb=0,
-                       Cf=self.gp(pre + '/reconstruct/kernel'), colsum=self.gp(pre + '/reconstruct/bias'),
-                       stream=ss)
+                       Cf=self.gp(pre + '/reconstruct/kernel'), colsum=self.gp(pre + '/reconstruct/bias'))
             t()
             t = self._tick('dec_dX')
             self._gemm(nr, d, V, L.ptr(dz), V, self.w(pre + '/reconstruct/kernel'), V, ta=0, tb=1,
@@ -1101,7 +845,6 @@ class Trainer:
             self._dense_bwd(self.D2, self.gD3, rows, 256, d, pre + '/decoded_3', gIn=self.gD2, mask=self.D2)
             self._dense_bwd(self.D1, self.gD2, rows, 128, 256, pre + '/decoded_2', gIn=self.gD1, mask=self.D1)
             self._dense_bwd(self.Zl, self.gD1, rows, 64, 128, pre + '/decoded_1', gIn=self.gZl, mask=self.Zl)
-        self._join()               # (the side stream's output-layer work before the bucket's exchange)
         self._fire('hook_out')
         self._fire('hook_dx')
 
@@ -1119,28 +862,23 @@ class Trainer:
     def bucket_hook_names(self):
         """Gradient buckets forward_backward_b finalises one by one and fires a hook for (zero.py
         starts each one's exchange there): W1's row chunks (the last with the towers)."""
-        if not self.layout.group_biases:
-            return ()
-        return tuple(f'w1_{i}' for i in range(len(self.layout.w1_chunks)))
+        return self.plan.bucket_hook_names
 
     def f_bucket_name(self):
         """The bucket whose sharded Adam launch also draws the next step's F (its update waits for
         the end of backward, as F must): the last W1 chunk, or the towers + E1 bucket."""
-        if self.layout.group_biases:
-            return f'w1_{len(self.layout.w1_chunks) - 1}'
-        return 'towers_e1'
+        return self.plan.f_bucket_name
 
     def _dx(self, gx, r0, nr, splits, pre, s, k=0):
-        """Decoder dX split-K partials into split_buf: the LDS-DMA pipelined kernel (dxgemm.hip)
-        on the bf16 shapes it takes (the full-mode regulariser's with Wo's fragment image), else
-        cc_gemm's register-staged NT path (same partials)."""
+        """Decoder dX split-K partials into split_buf behind a fused output kernel, by the kernel
+        the plan chose for the branch (plan.py: dx_kernels)."""
         d, V = self.cfg.d, self.cfg.V
         A, lda = self._dz_of(r0)
-        if k == 1 and self.WoP is not None and nr % 128 == 0 and dx_splitk_fits(nr, V, d):
+        kernel = self.plan.dx_kernels[k]
+        if kernel == 'dx_splitk_pk':
             L.call('cc_gemm_dx_splitk_pk', L.ptr(A), lda, L.ptr(self.WoP), nr, d, V, splits,
                    L.ptr(self.split_buf), s)
-        elif (self.dx_glds and not self.mx8 and nr % 128 == 0 and d % 128 == 0 and V % 8 == 0
-                and dx_splitk_fits(nr, V, d)):
+        elif kernel == 'dx_splitk':
             L.call('cc_gemm_dx_splitk', L.ptr(A), lda, self.w(pre + '/reconstruct/kernel'), V,
                    nr, d, V, splits, L.ptr(self.split_buf), s)
         else:
@@ -1233,14 +971,11 @@ class Trainer:
             else:
                 L.call('cc_tower_bwd_chain', L.C.byref(self.targs), s)
             t()
-            ss = self._fork()      # per-block dW slabs + their reduce overlap the E1 scatter
-            # direct dW: from the packed images (any row count) or LDS-staged (rows <= ~1184)
-            direct = self.hpt is not None or max(R, cfg.batch_size) <= 1184
-            if self.dtype == L.CC_BF16 and direct:
-                L.call('cc_tower_bwd_dw_direct', L.C.byref(self.targs), ss)
-            else:
-                L.call('cc_tower_bwd_dw', L.C.byref(self.targs), ss)
-                L.call('cc_tower_reduce', L.C.byref(self.targs), ss)
+            if self.plan.tower_dw == 'direct':   # bf16: dW straight from the packed images
+                L.call('cc_tower_bwd_dw_direct', L.C.byref(self.targs), s)
+            else:                                # per-block dW slabs + their reduce
+                L.call('cc_tower_bwd_dw', L.C.byref(self.targs), s)
+                L.call('cc_tower_reduce', L.C.byref(self.targs), s)
         else:
             self._dense_bwd(self.H3, self.gZl, (0, R), 128, 64, 'encoder/bottleneck', gIn=self.gH3, mask=self.H3)
             self._dense_bwd(self.H2, self.gH3, (0, R), 256, 128, 'encoder/encoded_3', gIn=self.gH2, mask=self.H2)
@@ -1248,7 +983,7 @@ class Trainer:
         t = self._tick('cc_embed_scatter_bwd')
         XR = self.xt_rows          # rows in the bitmask product (full mode: the cubes only)
         chunks = self.layout.w1_chunks if self.layout.group_biases else [(0, V)]
-        if self.eg_tickets is not None and self.fuse_w1:   # column slices + TF Adam on W1 in the epilogue
+        if self.fuse_w1:   # column slices + TF Adam on W1 in the epilogue
             cfg_ = self.cfg
             src, pk = (self.gpre1p, 1) if self.gpre1p is not None else (self.gPre1T, 0)
             if self.reg_by_index:   # + the reg rows by index (rows B .. of the dPre1 image)
@@ -1278,12 +1013,6 @@ class Trainer:
                            L.ptr(self.grads[gw + r0 * d:]), gbi, self._eg_tk(), s)
                 if i + 1 < len(chunks):
                     self._fire_bucket(f'w1_{i}')
-        elif self.gpre1p is not None:
-            L.call('cc_embed_grad_packed', L.ptr(self.gpre1p), V, d, XR, self.RP, L.ptr(self.xt_bits),
-                   self.gp('encoder/encoded_1/kernel'), self.gp('encoder/encoded_1/bias'), s)
-        elif self.embed_mfma:
-            L.call('cc_embed_grad_mfma', L.ptr(self.gPre1T), V, d, XR, self.RP, L.ptr(self.xt_bits),
-                   self.gp('encoder/encoded_1/kernel'), self.gp('encoder/encoded_1/bias'), s)
         else:
             L.call('cc_embed_scatter_bwd', L.ptr(self.gPre1), V, d, XR, L.ptr(self.xt_bits),
                    self.gp('encoder/encoded_1/kernel'), self.gp('encoder/encoded_1/bias'), s)
@@ -1293,9 +1022,7 @@ class Trainer:
                    self.reg_rows[1] - self.reg_rows[0], d, self.reg_rows[0],
                    self.gp('encoder/encoded_1/kernel'), self.gp('encoder/encoded_1/bias'), L.ptr(self.id_ws), s)
         t()
-        if self.fused_tower:       # the towers' dW (side stream) ride in the last W1 chunk's bucket
-            self._join()
-        for i in range(len(chunks)):   # (the W1 chunks not fired above: the last, or all of them)
+        for i in range(len(chunks)):   # (the W1 chunks not fired above: the last — the towers' dW rides in its bucket — or all of them)
             self._fire_bucket(f'w1_{i}')
 
     def _eg_tk(self):
@@ -1337,8 +1064,7 @@ class Trainer:
         t()
 
     def apply_rest(self, stream=None, defer=False):
-        """Advance the device step/epoch counters and refresh the transposed operand copies
-        (the decoder's Wo^T on the side stream, concurrently)."""
+        """Advance the device step/epoch counters and refresh the transposed operand copies."""
         if self.adam_packs:   # packed tower images already written by the Adam launch
             self.refresh_decoder_operands(L.stream_ptr(stream))
             if defer:         # counters: in the next forward's E1 gather launch
@@ -1347,11 +1073,9 @@ class Trainer:
                 L.call('cc_state_advance', L.ptr(self.state), self.batches_per_epoch, L.stream_ptr(stream))
             return
         if self.fused_tower and stream is None:
-            ss = self._fork()
-            self.refresh_decoder_operands(ss)
+            self.refresh_decoder_operands(L.stream_ptr(None))
             L.call('cc_tower_transpose_advance', L.C.byref(self.targs), L.ptr(self.state),
                    self.batches_per_epoch, L.stream_ptr(None))
-            self._join()
             return
         L.call('cc_state_advance', L.ptr(self.state), self.batches_per_epoch, L.stream_ptr(stream))
         self.transpose_tower(stream)
@@ -1438,15 +1162,14 @@ class Trainer:
         """zero.py may defer the output layers' all-gather to the next step's head: nothing between
         this step's Adam and the next D1 launch reads the output layers' shadow (the decoder kernels
         read Wo straight from it; no Wo^T, MX-FP8 or fragment image is refreshed from it)."""
-        return bool(self.cfg.dp_defer_out and self.fused_out and (not self.use_reg or self.fused_reg)
-                    and self.WoP is None and not self.mx8)
+        return self.plan.dp_defer_out_ok
 
     def flush(self, stream=None, defer=False):
         """Run the previous step's deferred counters/transposes (before reading state or the
         transposed operands from outside the step) and, data parallel, a deferred output-layer
         all-gather (a collective: every rank calls flush).  defer (forward_backward only): the
         counter advance may ride in the forward's first launch."""
-        if getattr(self, 'sharded', None) is not None:
+        if self.sharded is not None:
             self.sharded.flush_out()
         if self.pending_rest:
             self.pending_rest = False

@@ -711,3 +711,36 @@ def test_tower_forward_writes_target_mask_image(V, B):
     row = 8 * (pos >> 3) + 4 * (pos & 1) + ((pos >> 1) & 3)
     want = tr.y_bits[(torch.arange(B // 32)[:, None] * 32 + row[None, :]).reshape(-1).cuda()].t().contiguous()
     assert torch.equal(tr.y_img.view((V + 31) // 32, B), want)
+
+
+_HAS = {'has_wpack': 'wpack', 'has_D3p': 'D3p', 'has_gpre1p': 'gpre1p', 'has_w1_cs': 'eg_tickets',
+        'has_WoP': 'WoP', 'has_y_img': 'y_img', 'has_x_bits': 'x_bits', 'has_Z2': 'Z2'}
+
+
+@pytest.mark.parametrize('dtype,V,d,B,reg,kw', [
+    ('bf16', 700, 128, 128, 0.1, {}),
+    ('bf16', 2504, 256, 128, 0.0, dict(fuse_w1_adam=True, wo_adam_in_tower=True, f_in_tower=True)),
+    ('fp32', 300, 64, 32, 0.1, {}),
+    ('fp8', 700, 128, 128, 0.1, {}),
+    ('bf16', 300, 128, 128, 0.1, dict(reg_mode='full'))])
+def test_trainer_runs_the_planned_paths(dtype, V, d, B, reg, kw):
+    """The trainer is what plan.plan_step decided (tests/test_step_plan.py pins the plan itself on
+    the CPU): after construction and one step, every plan flag equals the attribute of the same name
+    and every has_* flag says whether its buffer exists."""
+    import dataclasses
+    tr, *_ = _setup(V, d, B, 4 * B, reg, dtype, **kw)
+    tr.step()
+    torch.cuda.synchronize()
+    tr.check_status()
+    assert np.isfinite(tr.losses()['loss'])
+    plain = lambda x: [plain(v) for v in x] if isinstance(x, (list, tuple)) else x   # noqa: E731
+    for f in dataclasses.fields(tr.plan):
+        want = getattr(tr.plan, f.name)
+        if f.name in _HAS:
+            assert (getattr(tr, _HAS[f.name]) is not None) == want, f.name
+        elif f.name in ('dp_defer_out_ok', 'bucket_hook_names', 'f_bucket_name'):
+            assert getattr(tr, f.name)() == want, f.name
+        elif f.name in ('layout', 'std_layout'):
+            assert getattr(tr, f.name) is want, f.name
+        elif f.name not in ('tower_dw', 'dx_kernels'):   # (read from the plan at their launches)
+            assert plain(getattr(tr, f.name)) == plain(want), f.name
