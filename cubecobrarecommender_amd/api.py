@@ -52,6 +52,22 @@ def get_model(path):
         return _models[path]
 
 
+def recommend_many(model, cubes_indices, amount, int_to_card):
+    """`recommend` in JSON mode for many cubes at once (Recommender.recommend_many): a list of
+    {"additions": {name: p}, "cuts": {name: p}}, one per cube, equal to the single-cube results."""
+    cubes_indices = [list(c) for c in cubes_indices]
+    outs = model.recommender().recommend_many(cubes_indices, amount)
+    result = []
+    for cube_indices, out in zip(cubes_indices, outs):
+        output = {'additions': {}, 'cuts': {}}
+        for idx, p in zip(out['additions'].tolist(), out['add_vals'].tolist()):
+            output['additions'][int_to_card[idx]] = p
+        for idx, p in zip(list(cube_indices), out['cut_vals'].tolist()):
+            output['cuts'][int_to_card[idx]] = p
+        result.append(output)
+    return result
+
+
 def recommend(model, cube_indices, amount, int_to_card, non_json=False, print_fn=print, print_cuts=True):
     """ml_recommend.py:78-116 / ml_recommend_web.py:39-67 on the GPU.  Returns
     {"additions": {name: p}, "cuts": {name: p}} (additions empty in non_json mode, as the reference

@@ -302,6 +302,29 @@ extern "C" int cc_infer_decode_fp32(const float *params, int32_t V, int32_t d, i
   return CC_OK;
 }
 
+// ---------------------------------------------------------------------- pieces for recbatch.hip
+namespace cc {
+int infer_check_d(int d, const char *who) { return check_d(d, who); }
+int infer_gather_cap(int max_n) { return gather_cap(max_n); }
+
+// E1 + both towers for R CSR rows: zlat [R, 64] and h3 [R, d]; part: [R][gather_cap(max_n)][d].
+int infer_h3_launch(const float *params, int V, int d, int R, const int32_t *row_ptr,
+                    const int32_t *idx, int max_n, float *part, float *zlat, float *h3,
+                    hipStream_t s) {
+  Tower T;
+  if (int rc = make_tower(params, V, d, T)) return rc;
+  const int cap = gather_cap(max_n);
+  const tiles::Req none{nullptr, nullptr, 0, 0};
+  hipLaunchKernelGGL(gather_partials_kernel, dim3(std::min(cap, 64), R), dim3(GNT), 0, s, T.W1, d,
+                     row_ptr, idx, none, cap, part, (uint32_t *)nullptr, (int64_t)0);
+  CC_LAUNCH_CHECK("gather_partials_kernel");
+  hipLaunchKernelGGL(tower_kernel, dim3(R), dim3(NT), tower_lds_bytes(d), s, T, 2, row_ptr, none,
+                     (uint32_t *)nullptr, (const float *)part, cap, (const float *)nullptr, zlat, h3);
+  CC_LAUNCH_CHECK("tower_kernel(batch)");
+  return CC_OK;
+}
+}  // namespace cc
+
 // ---------------------------------------------------------------------- single-cube request
 // ws layout: [partials gather_cap(V)*d floats][zlat 64][h3 d] | top-N sort workspace
 static size_t req_float_part(int V, int d) {

@@ -1,0 +1,374 @@
+// cc_recommend_batch_fp32 — R cubes per call, every row bit-identical to cc_recommend_fp32 on it.
+//
+// The single-cube output layer (infer.hip: out_kernel) streams the whole of Wo once per row; a
+// batch shares it.  E1 and the towers reuse gather_partials_kernel + tower_kernel (mode 2, one
+// workgroup per row) for h3 [R, d]; the rest is here:
+//   row_bits_kernel : one workgroup per row clears the row's cube bitmask and sets it from the
+//                     row's ids (nothing in the workspace survives from an earlier call).
+//   out_tile_kernel : one workgroup per tile of 16*RM rows x 64 cards.  K is streamed: 32 k of
+//                     Wo [32 k][64 cards] and of h3 [rows][32 k] are staged in LDS at a time and
+//                     shared by all the tile's rows (24 KB at 128 rows: four workgroups per CU); a
+//                     thread owns RM rows x 4 cards, one chunk accumulator and one running total
+//                     each, so any d fits.  The compiler pairs the cards into v_pk_mul_f32 /
+//                     v_pk_add_f32.  Arithmetic per (row, card) is out_kernel's, in the pinned
+//                     64-wide chunks: acc = acc + h[k]*W[k][n]
+//                     from 0 inside a chunk, chunk partials added in order from 0, + bo[n],
+//                     det_sigmoid32; multiply and add separately rounded (no contraction, so no
+//                     MFMA).  Writes the sort key of every card, the probability of every cube
+//                     card into its cut-value slot (binary search of the row's sorted ids), and
+//                     the probabilities only on request.
+//   topn_rows_kernel: one workgroup per row.  The composite (key' << 32 | card) is unique, so
+//                     the want largest are a radix SELECT of the want-th largest composite (10-bit
+//                     digits from the top, LDS histograms, suffix scan; stops as soon as the
+//                     chosen bin holds exactly the remaining count) and a bitonic sort of the
+//                     survivors in LDS — descending composite = descending probability, equal
+//                     probabilities higher card index first; cube cards (key' = 0) never make it
+//                     because want <= V - n.
+#include "common.hpp"
+#include "detmath.hpp"
+#include "topn_tiles.hpp"
+
+namespace cc {
+int param_offsets(int V, int d, int64_t *off, int64_t *size, int64_t *total, int64_t *main_total);
+// infer.hip
+int infer_check_d(int d, const char *who);
+int infer_gather_cap(int max_n);
+int infer_h3_launch(const float *params, int V, int d, int R, const int32_t *row_ptr,
+                    const int32_t *idx, int max_n, float *part, float *zlat, float *h3,
+                    hipStream_t s);
+}  // namespace cc
+
+namespace {
+
+constexpr int KCH = 64;      // dot chunk (pinned)
+constexpr int KS = 32;       // k per LDS stage of the output tile
+constexpr int TC = 64;       // cards per output tile
+constexpr int ONT = 256;     // output-tile workgroup: 16 card groups x 16 row groups
+constexpr int SNT = 1024;    // top-N workgroup
+constexpr int MAX_AMOUNT = 2048;  // survivors sorted in LDS
+
+__device__ __forceinline__ float addf(float a, float b) {
+#pragma clang fp contract(off)
+  return a + b;
+}
+__device__ __forceinline__ float mulf(float a, float b) {
+#pragma clang fp contract(off)
+  return a * b;
+}
+
+__global__ __launch_bounds__(256) void row_bits_kernel(const int32_t *__restrict__ row_ptr,
+                                                       const int32_t *__restrict__ idx, int V,
+                                                       int VW, uint32_t *__restrict__ bits) {
+  const int r = blockIdx.x;
+  uint32_t *b = bits + (int64_t)r * VW;
+  for (int i = threadIdx.x; i < VW; i += 256) b[i] = 0u;
+  __syncthreads();
+  const int beg = row_ptr[r], end = row_ptr[r + 1];
+  for (int i = beg + (int)threadIdx.x; i < end; i += 256) {
+    const int j = idx[i];
+    if ((uint32_t)j < (uint32_t)V) atomicOr(&b[j >> 5], 1u << (j & 31));
+  }
+}
+
+template <int RM>
+__global__ __launch_bounds__(ONT) void out_tile_kernel(
+    const float *__restrict__ h3, const float *__restrict__ Wo, const float *__restrict__ bo, int d,
+    int V, int R, const int32_t *__restrict__ row_ptr, const int32_t *__restrict__ idx,
+    const uint32_t *__restrict__ bits, int VW, uint32_t *__restrict__ keys, int Vs,
+    float *__restrict__ cut_vals, float *__restrict__ probs) {
+  constexpr int TR = 16 * RM;
+  // LDS stage: KS of a chunk's 64 k at a time (the chunk accumulator runs across its stages), so
+  // that four workgroups fit a CU
+  __shared__ __attribute__((aligned(16))) float wsm[KS][TC];
+  __shared__ __attribute__((aligned(16))) float hsm[TR][KS];
+  const int tid = threadIdx.x;
+  const int tx = tid & 15, ty = tid >> 4;
+  const int nb = blockIdx.x * TC;  // first card of the tile
+  const int rb = blockIdx.y * TR;  // first row of the tile
+  float tot[RM][4], acc[RM][4];
+#pragma unroll
+  for (int j = 0; j < RM; ++j)
+#pragma unroll
+    for (int e = 0; e < 4; ++e) tot[j][e] = acc[j][e] = 0.f;
+
+  for (int k0 = 0; k0 < d; k0 += KS) {
+    __syncthreads();  // the previous stage's readers are done
+    {
+      const int n = tid & 63, gn = nb + n;
+      const float *Wp = Wo + ((int64_t)k0 + (tid >> 6)) * V + gn;
+      float w[KS / 4];
+#pragma unroll
+      for (int i = 0; i < KS / 4; ++i) w[i] = gn < V ? Wp[(int64_t)(4 * i) * V] : 0.f;
+      constexpr int Q = KS / 4, RS = ONT / Q;  // float4 per row, rows per step
+      float4 h[TR / RS];
+#pragma unroll
+      for (int i = 0; i < TR / RS; ++i) {
+        const int gr = rb + tid / Q + RS * i;
+        h[i] = gr < R ? *reinterpret_cast<const float4 *>(h3 + (int64_t)gr * d + k0 + 4 * (tid % Q))
+                      : make_float4(0.f, 0.f, 0.f, 0.f);
+      }
+#pragma unroll
+      for (int i = 0; i < KS / 4; ++i) wsm[4 * i + (tid >> 6)][n] = w[i];
+#pragma unroll
+      for (int i = 0; i < TR / RS; ++i)
+        *reinterpret_cast<float4 *>(&hsm[tid / Q + RS * i][4 * (tid % Q)]) = h[i];
+    }
+    __syncthreads();
+#pragma unroll 2
+    for (int k4 = 0; k4 < KS / 4; ++k4) {
+      float4 w[4];
+#pragma unroll
+      for (int kk = 0; kk < 4; ++kk) w[kk] = *reinterpret_cast<const float4 *>(&wsm[4 * k4 + kk][4 * tx]);
+#pragma unroll
+      for (int j = 0; j < RM; ++j) {
+        const float4 h = *reinterpret_cast<const float4 *>(&hsm[ty * RM + j][4 * k4]);
+        const float hk[4] = {h.x, h.y, h.z, h.w};
+#pragma unroll
+        for (int kk = 0; kk < 4; ++kk) {
+          acc[j][0] = addf(acc[j][0], mulf(hk[kk], w[kk].x));
+          acc[j][1] = addf(acc[j][1], mulf(hk[kk], w[kk].y));
+          acc[j][2] = addf(acc[j][2], mulf(hk[kk], w[kk].z));
+          acc[j][3] = addf(acc[j][3], mulf(hk[kk], w[kk].w));
+        }
+      }
+    }
+    if ((k0 + KS) % KCH == 0) {  // a pinned chunk ends: its partial joins the total
+#pragma unroll
+      for (int j = 0; j < RM; ++j)
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+          tot[j][e] = addf(tot[j][e], acc[j][e]);
+          acc[j][e] = 0.f;
+        }
+    }
+  }
+
+  const int n0 = nb + 4 * tx;
+  if (n0 >= V) return;
+  float bias[4];
+#pragma unroll
+  for (int e = 0; e < 4; ++e) bias[e] = n0 + e < V ? bo[n0 + e] : 0.f;
+#pragma unroll
+  for (int j = 0; j < RM; ++j) {
+    const int gr = rb + ty * RM + j;
+    if (gr >= R) continue;
+    const uint32_t word = bits[(int64_t)gr * VW + (n0 >> 5)];  // n0 % 4 == 0: one word for all 4
+    uint32_t key[4];
+    float p[4];
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+      p[e] = detm::det_sigmoid32(addf(tot[j][e], bias[e]));
+      key[e] = tiles::key_of(p[e], (word >> ((n0 + e) & 31)) & 1u);
+    }
+    uint32_t *kr = keys + (int64_t)gr * Vs + n0;  // Vs % 4 == 0: 16-B aligned, the pad is ours
+    *reinterpret_cast<uint4 *>(kr) = make_uint4(key[0], key[1], key[2], key[3]);
+    if (probs) {
+#pragma unroll
+      for (int e = 0; e < 4; ++e)
+        if (n0 + e < V) probs[(int64_t)gr * V + n0 + e] = p[e];
+    }
+    if ((word >> (n0 & 31)) & 0xFu) {  // a cube card among the 4: its cut-value slot
+      const int beg = row_ptr[gr], end = row_ptr[gr + 1];
+#pragma unroll
+      for (int e = 0; e < 4; ++e) {
+        if (!((word >> ((n0 + e) & 31)) & 1u) || n0 + e >= V) continue;
+        int lo = beg, hi = end;  // first position with idx >= card
+        while (lo < hi) {
+          const int mid = (lo + hi) >> 1;
+          if (idx[mid] < n0 + e) lo = mid + 1; else hi = mid;
+        }
+        if (lo < end && idx[lo] == n0 + e) cut_vals[lo] = p[e];
+      }
+    }
+  }
+}
+
+// Inclusive scan of one int per thread over the SNT-thread block; wtot: [SNT/64] LDS scratch.
+__device__ __forceinline__ int block_incl_scan(int v, int *wtot) {
+  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+  int x = v;
+#pragma unroll
+  for (int off = 1; off < 64; off <<= 1) {
+    const int y = __shfl_up(x, off, 64);
+    if (lane >= off) x += y;
+  }
+  if (lane == 63) wtot[w] = x;
+  __syncthreads();
+  int before = 0;
+#pragma unroll
+  for (int i = 0; i < SNT / 64; ++i) before += i < w ? wtot[i] : 0;
+  __syncthreads();
+  return before + x;
+}
+
+__global__ __launch_bounds__(SNT) void topn_rows_kernel(const uint32_t *__restrict__ keys, int Vs,
+                                                        int V, const int32_t *__restrict__ row_ptr,
+                                                        int amount, int A,
+                                                        int32_t *__restrict__ n_add,
+                                                        int32_t *__restrict__ additions,
+                                                        float *__restrict__ add_vals) {
+  __shared__ uint32_t hist[1024];
+  __shared__ int wtot[SNT / 64];
+  __shared__ uint64_t s_prefix, s_mask;
+  __shared__ int s_rem, s_done, s_cnt;
+  __shared__ uint64_t sel[MAX_AMOUNT];
+  const int tid = threadIdx.x;
+  const int r = blockIdx.x;
+  const int n = row_ptr[r + 1] - row_ptr[r];
+  const int want = max(0, min(min(amount > 0 ? amount : 1, V - n), MAX_AMOUNT));
+  int32_t *adds = additions + (int64_t)r * A;
+  float *addv = add_vals + (int64_t)r * A;
+  for (int i = want + tid; i < A; i += SNT) {  // the unused tail
+    adds[i] = -1;
+    addv[i] = 0.f;
+  }
+  if (tid == 0) n_add[r] = want;
+  if (want == 0) return;
+  const uint32_t *k = keys + (int64_t)r * Vs;
+  if (tid == 0) {
+    s_prefix = 0;
+    s_mask = 0;
+    s_rem = want;
+    s_done = 0;
+    s_cnt = 0;
+  }
+  __syncthreads();
+  // composite bits: key' in 32..61 (key' < 2^30), card in 0..31; digits from the top
+  for (int pass = 0; pass < 7; ++pass) {
+    const int shift = pass < 6 ? 52 - 10 * pass : 0;
+    const uint32_t dmask = pass < 6 ? 1023u : 3u;
+    if (shift < 32 && ((uint32_t)(V - 1) >> shift) == 0u) continue;  // no card has a bit up here
+    if (s_done) break;
+    const uint64_t prefix = s_prefix, mask = s_mask;
+    const int rem = s_rem;
+    hist[tid] = 0u;
+    __syncthreads();
+    for (int j = tid; j < V; j += SNT) {
+      const uint64_t cmp = ((uint64_t)k[j] << 32) | (uint32_t)j;
+      if ((cmp & mask) == prefix) atomicAdd(&hist[(uint32_t)(cmp >> shift) & dmask], 1u);
+    }
+    __syncthreads();
+    // thread t owns bin 1023 - t: its inclusive scan is the count of matching items in bins >= it
+    const int v = (int)hist[1023 - tid];
+    const int ge = block_incl_scan(v, wtot), gt = ge - v;
+    if (ge >= rem && gt < rem) {  // exactly one bin: the one holding the rem-th largest
+      s_prefix = prefix | ((uint64_t)(1023 - tid) << shift);
+      s_mask = mask | ((uint64_t)dmask << shift);
+      s_rem = rem - gt;
+      s_done = v == rem - gt;  // the whole bin is wanted: every composite >= the prefix is in
+    }
+    __syncthreads();
+  }
+  const uint64_t T = s_prefix;
+  for (int j = tid; j < V; j += SNT) {
+    const uint64_t cmp = ((uint64_t)k[j] << 32) | (uint32_t)j;
+    if (cmp >= T) {
+      const int pos = atomicAdd(&s_cnt, 1);
+      if (pos < MAX_AMOUNT) sel[pos] = cmp;
+    }
+  }
+  __syncthreads();
+  int P = 1;
+  while (P < want) P <<= 1;
+  for (int i = min(s_cnt, want) + tid; i < P; i += SNT) sel[i] = 0ull;  // below every candidate
+  __syncthreads();
+  for (int size = 2; size <= P; size <<= 1)
+    for (int stride = size >> 1; stride > 0; stride >>= 1) {
+      for (int i = tid; i < P; i += SNT) {
+        const int pr = i ^ stride;
+        if (pr > i) {
+          const bool down = (i & size) == 0;
+          const uint64_t a = sel[i], b = sel[pr];
+          if ((a < b) == down) {
+            sel[i] = b;
+            sel[pr] = a;
+          }
+        }
+      }
+      __syncthreads();
+    }
+  for (int i = tid; i < want; i += SNT) {
+    const uint64_t cmp = sel[i];
+    adds[i] = (int32_t)(uint32_t)cmp;
+    addv[i] = __uint_as_float((uint32_t)(cmp >> 32) - 1u);
+  }
+}
+
+// workspace: [E1 partials R*cap*d][zlat R*64][h3 R*d][keys R*Vs][cube bitmasks R*VW]
+struct BatchWs {
+  size_t part, zlat, h3, keys, bits, total;
+  int Vs, VW;
+};
+BatchWs batch_ws(int V, int d, int R, int max_n) {
+  BatchWs w;
+  const size_t r = (size_t)std::max(R, 1), dd = (size_t)std::max(d, 64);
+  w.Vs = (std::max(V, 1) + 3) & ~3;
+  w.VW = (std::max(V, 1) + 31) / 32;
+  size_t o = 0;
+  w.part = o, o += tiles::align256(r * cc::infer_gather_cap(max_n) * dd * sizeof(float));
+  w.zlat = o, o += tiles::align256(r * 64 * sizeof(float));
+  w.h3 = o, o += tiles::align256(r * dd * sizeof(float));
+  w.keys = o, o += tiles::align256(r * w.Vs * sizeof(uint32_t));
+  w.bits = o, o += tiles::align256(r * w.VW * sizeof(uint32_t));
+  w.total = o;
+  return w;
+}
+
+template <int RM>
+void launch_out(dim3 grid, hipStream_t s, const float *h3, const float *Wo, const float *bo, int d,
+                int V, int R, const int32_t *row_ptr, const int32_t *idx, const uint32_t *bits,
+                int VW, uint32_t *keys, int Vs, float *cut_vals, float *probs) {
+  grid.y = (unsigned)cdiv(R, 16 * RM);
+  hipLaunchKernelGGL(out_tile_kernel<RM>, grid, dim3(ONT), 0, s, h3, Wo, bo, d, V, R, row_ptr, idx,
+                     bits, VW, keys, Vs, cut_vals, probs);
+}
+
+}  // namespace
+
+extern "C" int32_t cc_recommend_batch_max_amount(void) { return MAX_AMOUNT; }
+
+extern "C" size_t cc_recommend_batch_ws_size(int32_t V, int32_t d, int32_t R, int32_t max_n) {
+  return batch_ws(V, d, R, max_n).total + 256;
+}
+
+extern "C" int cc_recommend_batch_fp32(const float *params, int32_t V, int32_t d, int32_t R,
+                                       const int32_t *row_ptr, const int32_t *idx, int32_t max_n,
+                                       int32_t amount, void *ws, int32_t *n_add,
+                                       int32_t *additions, float *add_vals, float *cut_vals,
+                                       float *probs, void *stream) {
+  CC_REQUIRE(params && row_ptr && idx && ws && n_add && additions && add_vals && cut_vals,
+             "cc_recommend_batch_fp32: null pointer");
+  CC_REQUIRE(V > 0 && R >= 0 && max_n >= 0 && max_n <= V, "cc_recommend_batch_fp32: V/R/max_n");
+  if (int rc = cc::infer_check_d(d, "cc_recommend_batch_fp32")) return rc;
+  CC_REQUIRE(amount <= MAX_AMOUNT,
+             "cc_recommend_batch_fp32: amount above cc_recommend_batch_max_amount()");
+  CC_REQUIRE(((uintptr_t)ws & 255) == 0, "cc_recommend_batch_fp32: ws must be 256-byte aligned");
+  if (R == 0) return CC_OK;
+  int64_t off[CC_NUM_TENSORS], sz[CC_NUM_TENSORS], tot, mt;
+  if (int rc = cc::param_offsets(V, d, off, sz, &tot, &mt)) return rc;
+  const BatchWs w = batch_ws(V, d, R, max_n);
+  char *base = (char *)ws;
+  float *h3 = (float *)(base + w.h3);
+  uint32_t *keys = (uint32_t *)(base + w.keys), *bits = (uint32_t *)(base + w.bits);
+  hipStream_t s = as_stream(stream);
+  hipLaunchKernelGGL(row_bits_kernel, dim3(R), dim3(256), 0, s, row_ptr, idx, V, w.VW, bits);
+  CC_LAUNCH_CHECK("row_bits_kernel");
+  if (int rc = cc::infer_h3_launch(params, V, d, R, row_ptr, idx, max_n, (float *)(base + w.part),
+                                   (float *)(base + w.zlat), h3, s))
+    return rc;
+  const float *Wo = params + off[14], *bo = params + off[15];
+  const dim3 grid((unsigned)cdiv(V, TC), 1);
+  // rows per tile: 32 / 64 / 128 (the arithmetic per (row, card) does not depend on it)
+  if (R <= 32)
+    launch_out<2>(grid, s, h3, Wo, bo, d, V, R, row_ptr, idx, bits, w.VW, keys, w.Vs, cut_vals, probs);
+  else if (R <= 64)
+    launch_out<4>(grid, s, h3, Wo, bo, d, V, R, row_ptr, idx, bits, w.VW, keys, w.Vs, cut_vals, probs);
+  else
+    launch_out<8>(grid, s, h3, Wo, bo, d, V, R, row_ptr, idx, bits, w.VW, keys, w.Vs, cut_vals, probs);
+  CC_LAUNCH_CHECK("out_tile_kernel");
+  const int A = amount > 0 ? amount : 1;
+  hipLaunchKernelGGL(topn_rows_kernel, dim3(R), dim3(SNT), 0, s, (const uint32_t *)keys, w.Vs, V,
+                     row_ptr, amount, A, n_add, additions, add_vals);
+  CC_LAUNCH_CHECK("topn_rows_kernel");
+  return CC_OK;
+}

@@ -17,6 +17,55 @@ from .layout import Layout
 GRAPH_MAX_IDS = 4096   # cube ids per request the captured graph's H2D carries
 
 
+def check_card_ids(inputs, V):
+    """ValueError unless every id of every array of `inputs` is in [0, V); names the first cube."""
+    flat = np.concatenate(inputs) if len(inputs) else np.zeros(0, np.int64)
+    if not len(flat) or (flat.min() >= 0 and flat.max() < V):
+        return
+    for r, ci in enumerate(inputs):
+        if len(ci) and (ci.min() < 0 or ci.max() >= V):
+            raise ValueError(f'cube {r}: card index outside [0, {V})')
+
+
+def pack_cubes(cubes, V):
+    """R card-index lists -> the CSR that cc_recommend_batch_fp32 takes (pure host code, one sort
+    over all rows).
+
+    Returns (row_ptr int32 [R+1], idx int32 [row_ptr[R]], max_n, inputs, slot): row r of the CSR is
+    the sorted distinct ids of cubes[r]; inputs[r] is cubes[r] as an int64 array in the caller's
+    order, duplicates kept; slot [sum of len(inputs[r])] is, for every input entry in turn, the
+    position of its card in idx.  Raises ValueError for an id outside [0, V): the kernels index
+    the weights with these ids unchecked."""
+    inputs = [np.asarray(c, np.int64).reshape(-1) for c in cubes]
+    R = len(inputs)
+    lens = np.fromiter((len(ci) for ci in inputs), np.int64, R)
+    flat = np.concatenate(inputs) if R else np.zeros(0, np.int64)
+    rows = np.repeat(np.arange(R, dtype=np.int64), lens)
+    if len(flat) and (flat.min() < 0 or flat.max() >= V):
+        check_card_ids(inputs, V)
+    key = rows * V + flat                        # (row, card): equal entries are duplicates
+    order = np.argsort(key)
+    skey = key[order]
+    first = np.ones(len(skey), bool)
+    first[1:] = skey[1:] != skey[:-1]
+    ukey = skey[first]
+    slot = np.empty(len(skey), np.int64)
+    slot[order] = np.cumsum(first) - 1
+    counts = np.bincount(ukey // V, minlength=R) if R else np.zeros(0, np.int64)
+    row_ptr = np.zeros(R + 1, np.int32)
+    row_ptr[1:] = np.cumsum(counts)
+    idx = (ukey % V).astype(np.int32)
+    return row_ptr, idx, int(counts.max()) if R else 0, inputs, slot
+
+
+def cuts_in_input_order(cut_csr, slot, inputs):
+    """cut_csr (aligned with the CSR's idx) -> per cube, the values in the caller's input order
+    with duplicates repeated (pure host code)."""
+    vals = np.asarray(cut_csr, np.float32)[slot]
+    ends = np.cumsum([len(ci) for ci in inputs])
+    return [vals[e - len(ci):e] for ci, e in zip(inputs, ends)]
+
+
 class Recommender:
     def __init__(self, params_flat, V, d, device='cuda'):
         L.lib()
@@ -136,6 +185,72 @@ class Recommender:
             out['probs'] = probs.cpu().numpy()
         if want_order:
             out['order'] = order
+        return out
+
+    # ------------------------------------------------------------------ many cubes per call
+    def recommend_many(self, cubes, amount, want_probs=False, rows_per_launch=512):
+        """`recommend` for every cube of `cubes`, bit for bit, in launches of up to
+        rows_per_launch rows (cc_recommend_batch_fp32: one pass over the output layer per row
+        tile, one ranking workgroup per row).  Returns a list of dicts with the keys and dtypes of
+        `recommend`: additions, add_vals, cut_vals (input order, duplicates kept), probs on
+        request.  An id outside [0, V) raises ValueError before anything is launched.  Amounts
+        above cc_recommend_batch_max_amount() loop `recommend`; the results are the same."""
+        amount = int(amount)
+        rows_per_launch = max(1, int(rows_per_launch))
+        inputs = [np.asarray(c, np.int64).reshape(-1) for c in cubes]
+        R = len(inputs)
+        if R == 0:
+            return []
+        check_card_ids(inputs, self.V)
+        if amount > int(L.lib().cc_recommend_batch_max_amount()):
+            return [self.recommend(ci, amount, want_probs=want_probs) for ci in inputs]
+        V, d, dev = self.V, self.d, self.dev
+        A = max(amount, 1)
+        out = []
+
+        def launch(r0, r1):
+            """Pack rows r0..r1, queue their launch and the copies of its results to pinned
+            memory; no waiting."""
+            row_ptr, idx, max_n, _, slot = pack_cubes(inputs[r0:r1], V)
+            Rc, nnz = r1 - r0, len(idx)
+            need = int(L.lib().cc_recommend_batch_ws_size(V, d, Rc, max_n)) // 4 + 64
+            if getattr(self, '_batch_ws', None) is None or self._batch_ws.numel() < need:
+                self._batch_ws = torch.empty(need, device=dev, dtype=torch.int32)   # grown when needed, kept
+            rp_d = torch.from_numpy(row_ptr).to(dev, non_blocking=True)
+            ix_d = torch.from_numpy(idx if nnz else np.zeros(1, np.int32)).to(dev, non_blocking=True)
+            ints = torch.empty(Rc * (1 + A), device=dev, dtype=torch.int32)      # n_add, additions
+            flts = torch.empty(Rc * A + max(nnz, 1), device=dev, dtype=torch.float32)  # add_vals, cuts
+            probs = torch.empty(Rc, V, device=dev, dtype=torch.float32) if want_probs else None
+            L.call('cc_recommend_batch_fp32', L.ptr(self.params), V, d, Rc, L.ptr(rp_d), L.ptr(ix_d), max_n,
+                   amount, L.ptr(self._batch_ws), L.ptr(ints), L.ptr(ints[Rc:]), L.ptr(flts),
+                   L.ptr(flts[Rc * A:]), L.ptr(probs), L.stream_ptr(self.stream))
+            host = [torch.empty(t.shape, dtype=t.dtype, pin_memory=True).copy_(t, non_blocking=True)
+                    for t in ((ints, flts, probs) if want_probs else (ints, flts))]
+            done = torch.cuda.Event()
+            done.record(self.stream)
+            return r0, r1, nnz, slot, host, done
+
+        def collect(r0, r1, nnz, slot, host, done):
+            done.synchronize()
+            Rc = r1 - r0
+            ints, flts = host[0].numpy().copy(), host[1].numpy().copy()   # out of the pinned staging
+            nadd, adds, addv = ints[:Rc].tolist(), ints[Rc:].reshape(Rc, A), flts[:Rc * A].reshape(Rc, A)
+            cuts = cuts_in_input_order(flts[Rc * A:Rc * A + nnz], slot, inputs[r0:r1])
+            for r in range(Rc):
+                k = nadd[r]
+                o = {'additions': adds[r, :k], 'add_vals': addv[r, :k], 'cut_vals': cuts[r]}
+                if want_probs:
+                    o['probs'] = host[2][r].numpy().copy()
+                out.append(o)
+
+        with self.lock, torch.cuda.stream(self.stream):
+            pending = None      # a launch's results are unpacked while the next one runs
+            for r0 in range(0, R, rows_per_launch):
+                queued = launch(r0, min(R, r0 + rows_per_launch))
+                if pending is not None:
+                    collect(*pending)
+                pending = queued
+            collect(*pending)
         return out
 
     def _full_order(self, probs, uniq, amount):

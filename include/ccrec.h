@@ -680,6 +680,30 @@ int cc_recommend_graph_create(const float *params, int32_t V, int32_t d, const i
 int cc_recommend_graph_run(void *handle, int32_t *res_host, int32_t res_words);
 int cc_recommend_graph_destroy(void *handle);
 
+/* ----------------------------------------------------------------------------------
+ * R requests in one call; every row's results are bit-identical to cc_recommend_fp32 on that
+ * row.  One pass over the output layer serves a whole tile of rows, and one workgroup per row
+ * ranks it (radix select of the want-th largest (key, card) + a sort of the survivors).
+ *   row_ptr [R + 1], idx: CSR of the cubes' card ids (device), max_n >= the longest row.
+ *   PRECONDITIONS (the caller validates; an id outside [0, V) would be an out-of-bounds
+ *   read): ids sorted ascending and unique within a row, all in [0, V).
+ *   amount <= cc_recommend_batch_max_amount() (at least 1024); want_r = min(max(amount, 1),
+ *   V - n_r) with n_r the row's length; A = max(amount, 1).
+ *   n_add [R] = want_r; additions / add_vals [R][A]: the first want_r entries of row r in
+ *   rank order, the unused tail -1 / 0; cut_vals [row_ptr[R]] aligned with idx;
+ *   probs [R][V] or NULL.
+ *   ws: cc_recommend_batch_ws_size(V, d, R, max_n) bytes, 256-B aligned; the call does not
+ *   depend on its contents.  R == 0 returns CC_OK without a launch.
+ * CC_ERR_ARG: null pointer, d not a multiple of 64 in [64, 1024], amount above the limit,
+ * unaligned ws.
+ * ---------------------------------------------------------------------------------- */
+int32_t cc_recommend_batch_max_amount(void);
+size_t cc_recommend_batch_ws_size(int32_t V, int32_t d, int32_t R, int32_t max_n);
+int cc_recommend_batch_fp32(const float *params, int32_t V, int32_t d, int32_t R,
+                            const int32_t *row_ptr, const int32_t *idx, int32_t max_n,
+                            int32_t amount, void *ws, int32_t *n_add, int32_t *additions,
+                            float *add_vals, float *cut_vals, float *probs, void *stream);
+
 /* ---------------------------------------------------------------- card co-occurrence graph (N1)
  * Replaces src/non_ml/utils.py:75-91 (create_adjacency_matrix, called by
  * src/non_ml/create_mtx.py:19) and the M~ normalisation of src/ml/train.py:69-71.
