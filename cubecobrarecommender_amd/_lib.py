@@ -185,6 +185,9 @@ SIGNATURES = {
     'cc_recommend_batch_max_amount': (_I32, []),
     'cc_recommend_batch_ws_size': (_SZ, [_I32, _I32, _I32, _I32]),
     'cc_recommend_batch_fp32': (C.c_int, [_P, _I32, _I32, _I32, _P, _P, _I32, _I32, _P, _P, _P, _P, _P, _P, _P]),
+    'cc_recommend_batch_rank_ws_size': (_SZ, [_I32, _I32, _I32, _I32]),
+    'cc_recommend_batch_rank_fp32': (C.c_int, [_P, _I32, _I32, _I32, _P, _P, _I32, _I32, _P, _P, _P, _P, _P, _P,
+                                               _P]),
     'cc_adjacency_ws_size': (_SZ, [_I32, _I32, _I32, _I32]),
     'cc_adjacency': (C.c_int, [_P, _P, _I32, _I32, _I32, _P, _P, _P, _P, _P, _P]),
 }

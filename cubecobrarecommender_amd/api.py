@@ -54,7 +54,9 @@ def get_model(path):
 
 def recommend_many(model, cubes_indices, amount, int_to_card):
     """`recommend` in JSON mode for many cubes at once (Recommender.recommend_many): a list of
-    {"additions": {name: p}, "cuts": {name: p}}, one per cube, equal to the single-cube results."""
+    {"additions": {name: p}, "cuts": {name: p}}, one per cube, equal to the single-cube results.
+    Any amount stays on the batched path: above cc_recommend_batch_max_amount() (the web
+    endpoint's default of 30000 ranks every card) each row is sorted on the device."""
     cubes_indices = [list(c) for c in cubes_indices]
     outs = model.recommender().recommend_many(cubes_indices, amount)
     result = []

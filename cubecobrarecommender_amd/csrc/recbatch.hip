@@ -24,6 +24,10 @@
 //                     survivors in LDS — descending composite = descending probability, equal
 //                     probabilities higher card index first; cube cards (key' = 0) never make it
 //                     because want <= V - n.
+// cc_recommend_batch_rank_fp32 runs the same chain for any amount, with the select replaced by
+//   rank_rows_kernel: one workgroup per row sorts all V (key', card) pairs (stable LSD radix
+//                     sort, three 10-bit passes through two ping-pong buffers in the workspace)
+//                     and writes the first want entries of the descending order.
 #include "common.hpp"
 #include "detmath.hpp"
 #include "topn_tiles.hpp"
@@ -294,6 +298,134 @@ __global__ __launch_bounds__(SNT) void topn_rows_kernel(const uint32_t *__restri
   }
 }
 
+// Full ranking of one row: a stable LSD radix sort of ascending key' from ascending card order,
+// tiles::PASSES passes of tiles::BITS bits, one workgroup per row.  Wave w owns a contiguous slice
+// of the current arrangement; inside a wave the rank is a ballot multisplit, across waves the
+// exclusive scan of the (digit, wave) counts in digit-major order.  (key', card) pairs ping-pong
+// through pa / pb as one 64-bit word; the last pass stores nothing but the row's results:
+// ascending position pos is descending position V - 1 - pos, and the cube cards (key' = 0) hold
+// the first n ascending positions, i.e. the last n descending ones, which want <= V - n never
+// reaches.
+__device__ __forceinline__ uint64_t rank_load(const uint32_t *k, const uint64_t *src, int pass,
+                                               int i) {
+  return pass == 0 ? ((uint64_t)k[i] << 32) | (uint32_t)i : src[i];
+}
+// the valid lanes of the wave that hold digit dg
+__device__ __forceinline__ uint64_t rank_match(uint32_t dg, bool valid) {
+  uint64_t m = __ballot(valid);
+#pragma unroll
+  for (int bit = 0; bit < tiles::BITS; ++bit) {
+    const bool b = (dg >> bit) & 1u;
+    const uint64_t bb = __ballot(b);
+    m &= b ? bb : ~bb;
+  }
+  return m;
+}
+constexpr int RU = 8;  // items a lane loads ahead of ranking them: the loads' latency is paid once
+
+__global__ __launch_bounds__(SNT) void rank_rows_kernel(const uint32_t *__restrict__ keys, int Vs,
+                                                        int V, const int32_t *__restrict__ row_ptr,
+                                                        int amount, int A, uint64_t *pa,
+                                                        uint64_t *pb, int Vp,
+                                                        int32_t *__restrict__ n_add,
+                                                        int32_t *__restrict__ additions,
+                                                        float *__restrict__ add_vals) {
+  constexpr int NW = SNT / 64;
+  __shared__ uint32_t hist[NW * tiles::R];  // [wave][digit]: a thread scans its digit's column
+  __shared__ int wtot[NW];
+  const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+  const uint64_t lt = (1ull << lane) - 1ull;
+  const int r = blockIdx.x;
+  const int n = row_ptr[r + 1] - row_ptr[r];
+  const int want = max(0, min(amount > 0 ? amount : 1, V - n));
+  int32_t *adds = additions + (int64_t)r * A;
+  float *addv = add_vals + (int64_t)r * A;
+  for (int i = want + tid; i < A; i += SNT) {  // the unused tail
+    adds[i] = -1;
+    addv[i] = 0.f;
+  }
+  if (tid == 0) n_add[r] = want;
+  if (want == 0) return;
+  const uint32_t *k = keys + (int64_t)r * Vs;
+  uint64_t *bufa = pa + (int64_t)r * Vp, *bufb = pb + (int64_t)r * Vp;
+  const int S = (int)cdiv(cdiv(V, NW), 64) * 64;  // per-wave slice
+  const int lo = w * S, hi = min(V, lo + S);
+  uint32_t *hw = hist + w * tiles::R;
+  for (int pass = 0; pass < tiles::PASSES; ++pass) {
+    const uint64_t *src = (pass & 1) ? bufa : bufb;  // pass 0 reads the keys instead
+    uint64_t *dst = (pass & 1) ? bufb : bufa;
+    const bool last = pass == tiles::PASSES - 1;
+#pragma unroll
+    for (int i = 0; i < NW; ++i) hist[i * tiles::R + tid] = 0u;
+    __syncthreads();
+    for (int base0 = lo; base0 < hi; base0 += 64 * RU) {
+      uint64_t item[RU];
+#pragma unroll
+      for (int u = 0; u < RU; ++u) {
+        const int i = base0 + 64 * u + lane;
+        item[u] = i < hi ? rank_load(k, src, pass, i) : 0ull;
+      }
+#pragma unroll
+      for (int u = 0; u < RU; ++u) {
+        if (base0 + 64 * u >= hi) break;
+        const bool valid = base0 + 64 * u + lane < hi;
+        const uint32_t dg = tiles::digit((uint32_t)(item[u] >> 32), pass);
+        const uint64_t m = rank_match(dg, valid);
+        if (valid && (m & lt) == 0) hw[dg] += (uint32_t)__popcll(m);
+      }
+    }
+    __syncthreads();
+    {  // exclusive scan in (digit, wave) order; thread tid owns digit tid
+      uint32_t c[NW];
+      int s = 0;
+#pragma unroll
+      for (int i = 0; i < NW; ++i) {
+        c[i] = hist[i * tiles::R + tid];
+        s += (int)c[i];
+      }
+      int off = block_incl_scan(s, wtot) - s;
+#pragma unroll
+      for (int i = 0; i < NW; ++i) {
+        hist[i * tiles::R + tid] = (uint32_t)off;
+        off += (int)c[i];
+      }
+    }
+    __syncthreads();
+    for (int base0 = lo; base0 < hi; base0 += 64 * RU) {
+      uint64_t item[RU];
+#pragma unroll
+      for (int u = 0; u < RU; ++u) {
+        const int i = base0 + 64 * u + lane;
+        item[u] = i < hi ? rank_load(k, src, pass, i) : 0ull;
+      }
+#pragma unroll
+      for (int u = 0; u < RU; ++u) {
+        if (base0 + 64 * u >= hi) break;
+        const bool valid = base0 + 64 * u + lane < hi;
+        const uint32_t key = (uint32_t)(item[u] >> 32);
+        const uint32_t dg = tiles::digit(key, pass);
+        const uint64_t m = rank_match(dg, valid);
+        const uint32_t basepos = hw[dg];
+        const uint32_t pos = basepos + (uint32_t)__popcll(m & lt);
+        if (valid && pos < (uint32_t)V) {  // pos >= V needs inconsistent counts: never write there
+          if (last) {
+            const int q = V - 1 - (int)pos;  // descending position
+            if (q < want) {
+              adds[q] = (int32_t)(uint32_t)item[u];
+              addv[q] = __uint_as_float(key - 1u);
+            }
+          } else {
+            dst[pos] = item[u];
+          }
+        }
+        if (valid && (m & lt) == 0) hw[dg] = basepos + (uint32_t)__popcll(m);
+      }
+    }
+    __threadfence_block();
+    __syncthreads();
+  }
+}
+
 // workspace: [E1 partials R*cap*d][zlat R*64][h3 R*d][keys R*Vs][cube bitmasks R*VW]
 struct BatchWs {
   size_t part, zlat, h3, keys, bits, total;
@@ -331,26 +463,16 @@ extern "C" size_t cc_recommend_batch_ws_size(int32_t V, int32_t d, int32_t R, in
   return batch_ws(V, d, R, max_n).total + 256;
 }
 
-extern "C" int cc_recommend_batch_fp32(const float *params, int32_t V, int32_t d, int32_t R,
-                                       const int32_t *row_ptr, const int32_t *idx, int32_t max_n,
-                                       int32_t amount, void *ws, int32_t *n_add,
-                                       int32_t *additions, float *add_vals, float *cut_vals,
-                                       float *probs, void *stream) {
-  CC_REQUIRE(params && row_ptr && idx && ws && n_add && additions && add_vals && cut_vals,
-             "cc_recommend_batch_fp32: null pointer");
-  CC_REQUIRE(V > 0 && R >= 0 && max_n >= 0 && max_n <= V, "cc_recommend_batch_fp32: V/R/max_n");
-  if (int rc = cc::infer_check_d(d, "cc_recommend_batch_fp32")) return rc;
-  CC_REQUIRE(amount <= MAX_AMOUNT,
-             "cc_recommend_batch_fp32: amount above cc_recommend_batch_max_amount()");
-  CC_REQUIRE(((uintptr_t)ws & 255) == 0, "cc_recommend_batch_fp32: ws must be 256-byte aligned");
-  if (R == 0) return CC_OK;
+// The launches both entries share: cube bitmasks, h3, then the output layer, which leaves every
+// row's sort keys in the workspace, its cut values and (on request) its probabilities.
+static int batch_keys_launch(const float *params, int V, int d, int R, const int32_t *row_ptr,
+                             const int32_t *idx, int max_n, void *ws, const BatchWs &w,
+                             float *cut_vals, float *probs, hipStream_t s) {
   int64_t off[CC_NUM_TENSORS], sz[CC_NUM_TENSORS], tot, mt;
   if (int rc = cc::param_offsets(V, d, off, sz, &tot, &mt)) return rc;
-  const BatchWs w = batch_ws(V, d, R, max_n);
   char *base = (char *)ws;
   float *h3 = (float *)(base + w.h3);
   uint32_t *keys = (uint32_t *)(base + w.keys), *bits = (uint32_t *)(base + w.bits);
-  hipStream_t s = as_stream(stream);
   hipLaunchKernelGGL(row_bits_kernel, dim3(R), dim3(256), 0, s, row_ptr, idx, V, w.VW, bits);
   CC_LAUNCH_CHECK("row_bits_kernel");
   if (int rc = cc::infer_h3_launch(params, V, d, R, row_ptr, idx, max_n, (float *)(base + w.part),
@@ -366,9 +488,68 @@ extern "C" int cc_recommend_batch_fp32(const float *params, int32_t V, int32_t d
   else
     launch_out<8>(grid, s, h3, Wo, bo, d, V, R, row_ptr, idx, bits, w.VW, keys, w.Vs, cut_vals, probs);
   CC_LAUNCH_CHECK("out_tile_kernel");
+  return CC_OK;
+}
+
+extern "C" int cc_recommend_batch_fp32(const float *params, int32_t V, int32_t d, int32_t R,
+                                       const int32_t *row_ptr, const int32_t *idx, int32_t max_n,
+                                       int32_t amount, void *ws, int32_t *n_add,
+                                       int32_t *additions, float *add_vals, float *cut_vals,
+                                       float *probs, void *stream) {
+  CC_REQUIRE(params && row_ptr && idx && ws && n_add && additions && add_vals && cut_vals,
+             "cc_recommend_batch_fp32: null pointer");
+  CC_REQUIRE(V > 0 && R >= 0 && max_n >= 0 && max_n <= V, "cc_recommend_batch_fp32: V/R/max_n");
+  if (int rc = cc::infer_check_d(d, "cc_recommend_batch_fp32")) return rc;
+  CC_REQUIRE(amount <= MAX_AMOUNT,
+             "cc_recommend_batch_fp32: amount above cc_recommend_batch_max_amount()");
+  CC_REQUIRE(((uintptr_t)ws & 255) == 0, "cc_recommend_batch_fp32: ws must be 256-byte aligned");
+  if (R == 0) return CC_OK;
+  const BatchWs w = batch_ws(V, d, R, max_n);
+  hipStream_t s = as_stream(stream);
+  if (int rc = batch_keys_launch(params, V, d, R, row_ptr, idx, max_n, ws, w, cut_vals, probs, s))
+    return rc;
   const int A = amount > 0 ? amount : 1;
-  hipLaunchKernelGGL(topn_rows_kernel, dim3(R), dim3(SNT), 0, s, (const uint32_t *)keys, w.Vs, V,
-                     row_ptr, amount, A, n_add, additions, add_vals);
+  hipLaunchKernelGGL(topn_rows_kernel, dim3(R), dim3(SNT), 0, s,
+                     (const uint32_t *)((char *)ws + w.keys), w.Vs, V, row_ptr, amount, A, n_add,
+                     additions, add_vals);
   CC_LAUNCH_CHECK("topn_rows_kernel");
+  return CC_OK;
+}
+
+// rank workspace: the batch workspace, then the two (key', card) ping-pong buffers [R][Vp] of
+// 64-bit words; Vp is a multiple of 16, so no two rows share a 128-byte line
+static size_t rank_pitch(int V) { return ((size_t)std::max(V, 1) + 15) & ~(size_t)15; }
+static size_t rank_buf_bytes(int V, int R) {
+  return tiles::align256((size_t)std::max(R, 1) * rank_pitch(V) * sizeof(uint64_t));
+}
+
+extern "C" size_t cc_recommend_batch_rank_ws_size(int32_t V, int32_t d, int32_t R, int32_t max_n) {
+  return batch_ws(V, d, R, max_n).total + 2 * rank_buf_bytes(V, R) + 256;
+}
+
+extern "C" int cc_recommend_batch_rank_fp32(const float *params, int32_t V, int32_t d, int32_t R,
+                                            const int32_t *row_ptr, const int32_t *idx,
+                                            int32_t max_n, int32_t amount, void *ws,
+                                            int32_t *n_add, int32_t *additions, float *add_vals,
+                                            float *cut_vals, float *probs, void *stream) {
+  CC_REQUIRE(params && row_ptr && idx && ws && n_add && additions && add_vals && cut_vals,
+             "cc_recommend_batch_rank_fp32: null pointer");
+  CC_REQUIRE(V > 0 && R >= 0 && max_n >= 0 && max_n <= V,
+             "cc_recommend_batch_rank_fp32: V/R/max_n");
+  if (int rc = cc::infer_check_d(d, "cc_recommend_batch_rank_fp32")) return rc;
+  CC_REQUIRE(((uintptr_t)ws & 255) == 0,
+             "cc_recommend_batch_rank_fp32: ws must be 256-byte aligned");
+  if (R == 0) return CC_OK;
+  const BatchWs w = batch_ws(V, d, R, max_n);
+  hipStream_t s = as_stream(stream);
+  if (int rc = batch_keys_launch(params, V, d, R, row_ptr, idx, max_n, ws, w, cut_vals, probs, s))
+    return rc;
+  char *base = (char *)ws;
+  uint64_t *pa = (uint64_t *)(base + w.total), *pb = (uint64_t *)(base + w.total + rank_buf_bytes(V, R));
+  const int A = std::min(amount > 0 ? amount : 1, V);
+  hipLaunchKernelGGL(rank_rows_kernel, dim3(R), dim3(SNT), 0, s, (const uint32_t *)(base + w.keys),
+                     w.Vs, V, row_ptr, amount, A, pa, pb, (int)rank_pitch(V), n_add, additions,
+                     add_vals);
+  CC_LAUNCH_CHECK("rank_rows_kernel");
   return CC_OK;
 }

@@ -15,6 +15,7 @@ from . import _lib as L
 from .layout import Layout
 
 GRAPH_MAX_IDS = 4096   # cube ids per request the captured graph's H2D carries
+RANK_STAGING_BYTES = 128 << 20   # pinned result staging per launch of the full-ranking batched path
 
 
 def check_card_ids(inputs, V):
@@ -66,6 +67,14 @@ def cuts_in_input_order(cut_csr, slot, inputs):
     return [vals[e - len(ci):e] for ci, e in zip(inputs, ends)]
 
 
+def rank_rows_per_launch(V, A, rows_per_launch, budget_bytes=RANK_STAGING_BYTES, want_probs=False):
+    """Rows per launch of the full-ranking path (pure host code): at most rows_per_launch, at
+    least 1, and as many as keep one launch's pinned staging within budget_bytes.  A row stages
+    n_add, A additions, A values and up to V cut values (plus V probabilities on request)."""
+    per_row = 4 * (1 + 2 * int(A) + int(V) * (2 if want_probs else 1))
+    return max(1, min(int(rows_per_launch), int(budget_bytes) // per_row))
+
+
 class Recommender:
     def __init__(self, params_flat, V, d, device='cuda'):
         L.lib()
@@ -89,6 +98,7 @@ class Recommender:
         self._req_np = self.pin_req.numpy()
         self._res_np = self.pin_res.numpy()
         self._graph = None
+        self._rank_pins = {}    # recommend_many's pinned staging on the full-ranking path
         # the request graph runs on the library's own non-blocking stream: every allocation and
         # fill above (issued on torch's stream) must be complete before it can run
         torch.cuda.synchronize(self.dev)
@@ -194,7 +204,10 @@ class Recommender:
         tile, one ranking workgroup per row).  Returns a list of dicts with the keys and dtypes of
         `recommend`: additions, add_vals, cut_vals (input order, duplicates kept), probs on
         request.  An id outside [0, V) raises ValueError before anything is launched.  Amounts
-        above cc_recommend_batch_max_amount() loop `recommend`; the results are the same."""
+        above cc_recommend_batch_max_amount() take cc_recommend_batch_rank_fp32 (one sorting
+        workgroup per row, result rows of min(amount, V) entries): its launches are capped by
+        rank_rows_per_launch, and their results pass through two pinned staging buffers that the
+        Recommender keeps."""
         amount = int(amount)
         rows_per_launch = max(1, int(rows_per_launch))
         inputs = [np.asarray(c, np.int64).reshape(-1) for c in cubes]
@@ -202,18 +215,33 @@ class Recommender:
         if R == 0:
             return []
         check_card_ids(inputs, self.V)
-        if amount > int(L.lib().cc_recommend_batch_max_amount()):
-            return [self.recommend(ci, amount, want_probs=want_probs) for ci in inputs]
         V, d, dev = self.V, self.d, self.dev
-        A = max(amount, 1)
+        rank = amount > int(L.lib().cc_recommend_batch_max_amount())
+        if rank:
+            A = min(max(amount, 1), V)
+            rows_per_launch = rank_rows_per_launch(V, A, rows_per_launch, want_probs=want_probs)
+            entry, ws_size = 'cc_recommend_batch_rank_fp32', L.lib().cc_recommend_batch_rank_ws_size
+        else:
+            A = max(amount, 1)
+            entry, ws_size = 'cc_recommend_batch_fp32', L.lib().cc_recommend_batch_ws_size
         out = []
 
-        def launch(r0, r1):
+        def staged(t, key):
+            """A pinned host tensor receiving `t`: fresh on the select path; on the ranking path
+            a view of the kept buffer `key`, which grows when needed."""
+            if not rank:
+                return torch.empty(t.shape, dtype=t.dtype, pin_memory=True).copy_(t, non_blocking=True)
+            pins = self._rank_pins
+            if key not in pins or pins[key].numel() < t.numel():
+                pins[key] = torch.empty(t.numel(), dtype=t.dtype, pin_memory=True)
+            return pins[key][:t.numel()].view(t.shape).copy_(t, non_blocking=True)
+
+        def launch(r0, r1, turn):
             """Pack rows r0..r1, queue their launch and the copies of its results to pinned
-            memory; no waiting."""
+            memory (staging set `turn`); no waiting."""
             row_ptr, idx, max_n, _, slot = pack_cubes(inputs[r0:r1], V)
             Rc, nnz = r1 - r0, len(idx)
-            need = int(L.lib().cc_recommend_batch_ws_size(V, d, Rc, max_n)) // 4 + 64
+            need = int(ws_size(V, d, Rc, max_n)) // 4 + 64
             if getattr(self, '_batch_ws', None) is None or self._batch_ws.numel() < need:
                 self._batch_ws = torch.empty(need, device=dev, dtype=torch.int32)   # grown when needed, kept
             rp_d = torch.from_numpy(row_ptr).to(dev, non_blocking=True)
@@ -221,11 +249,11 @@ class Recommender:
             ints = torch.empty(Rc * (1 + A), device=dev, dtype=torch.int32)      # n_add, additions
             flts = torch.empty(Rc * A + max(nnz, 1), device=dev, dtype=torch.float32)  # add_vals, cuts
             probs = torch.empty(Rc, V, device=dev, dtype=torch.float32) if want_probs else None
-            L.call('cc_recommend_batch_fp32', L.ptr(self.params), V, d, Rc, L.ptr(rp_d), L.ptr(ix_d), max_n,
+            L.call(entry, L.ptr(self.params), V, d, Rc, L.ptr(rp_d), L.ptr(ix_d), max_n,
                    amount, L.ptr(self._batch_ws), L.ptr(ints), L.ptr(ints[Rc:]), L.ptr(flts),
                    L.ptr(flts[Rc * A:]), L.ptr(probs), L.stream_ptr(self.stream))
-            host = [torch.empty(t.shape, dtype=t.dtype, pin_memory=True).copy_(t, non_blocking=True)
-                    for t in ((ints, flts, probs) if want_probs else (ints, flts))]
+            host = [staged(t, (turn, i))
+                    for i, t in enumerate((ints, flts, probs) if want_probs else (ints, flts))]
             done = torch.cuda.Event()
             done.record(self.stream)
             return r0, r1, nnz, slot, host, done
@@ -245,8 +273,9 @@ class Recommender:
 
         with self.lock, torch.cuda.stream(self.stream):
             pending = None      # a launch's results are unpacked while the next one runs
-            for r0 in range(0, R, rows_per_launch):
-                queued = launch(r0, min(R, r0 + rows_per_launch))
+            for turn, r0 in enumerate(range(0, R, rows_per_launch)):
+                # a staging set is free again once the launch before last has been collected
+                queued = launch(r0, min(R, r0 + rows_per_launch), turn & 1)
                 if pending is not None:
                     collect(*pending)
                 pending = queued

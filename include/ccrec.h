@@ -704,6 +704,20 @@ int cc_recommend_batch_fp32(const float *params, int32_t V, int32_t d, int32_t R
                             int32_t amount, void *ws, int32_t *n_add, int32_t *additions,
                             float *add_vals, float *cut_vals, float *probs, void *stream);
 
+/* The same call for any amount: instead of the select, one workgroup per row sorts all V cards
+ * (stable LSD radix sort of key', three 10-bit passes) and writes the first want_r of the ranking.
+ * Arguments, preconditions and outputs are those of cc_recommend_batch_fp32 except:
+ *   any amount is valid (amount <= 0 means 1); the row pitch of additions / add_vals is
+ *   A = min(max(amount, 1), V), so a "rank everything" amount such as 30000 costs V words per row;
+ *   ws: cc_recommend_batch_rank_ws_size(V, d, R, max_n) bytes (the batch workspace plus two
+ *   (key', card) ping-pong buffers), 256-B aligned; the call does not depend on its contents.
+ * CC_ERR_ARG: null pointer, max_n > V, d not a multiple of 64 in [64, 1024], unaligned ws. */
+size_t cc_recommend_batch_rank_ws_size(int32_t V, int32_t d, int32_t R, int32_t max_n);
+int cc_recommend_batch_rank_fp32(const float *params, int32_t V, int32_t d, int32_t R,
+                                 const int32_t *row_ptr, const int32_t *idx, int32_t max_n,
+                                 int32_t amount, void *ws, int32_t *n_add, int32_t *additions,
+                                 float *add_vals, float *cut_vals, float *probs, void *stream);
+
 /* ---------------------------------------------------------------- card co-occurrence graph (N1)
  * Replaces src/non_ml/utils.py:75-91 (create_adjacency_matrix, called by
  * src/non_ml/create_mtx.py:19) and the M~ normalisation of src/ml/train.py:69-71.

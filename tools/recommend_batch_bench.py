@@ -11,6 +11,8 @@ R in {1, 8, 64, 512, 4096}.  Modes (cubes/s, wall clock including the host-side 
 of the repeats.  One JSON document on stdout (and in --out).
 
     python tools/recommend_batch_bench.py [--modes loop,compose,batch] [--rows 1,8,64,512,4096]
+                                          [--amount 100]
+--amount above every |V| (the web endpoint's default is 30000) ranks every card of every cube.
 """
 import argparse
 import json
@@ -50,8 +52,8 @@ def run_compose(rec, cubes):
     ptr = np.zeros(R + 1, np.int64)
     ptr[1:] = np.cumsum([len(u) for u in uniq])
     idx = torch.from_numpy(np.concatenate(uniq)).to(dev)
-    adds = torch.zeros(R, AMOUNT, device=dev, dtype=torch.int32)
-    addv = torch.zeros(R, AMOUNT, device=dev)
+    adds = torch.zeros(R, min(AMOUNT, V), device=dev, dtype=torch.int32)
+    addv = torch.zeros(R, min(AMOUNT, V), device=dev)
     cutv = torch.zeros(int(ptr[-1]), device=dev)
     nadd = torch.zeros(R, device=dev, dtype=torch.int32)
     ws = torch.zeros(int(L.lib().cc_topn_workspace_size(V)) // 4 + 64, device=dev, dtype=torch.int32)
@@ -71,12 +73,15 @@ MODES = {'loop': run_loop, 'compose': run_compose, 'batch': run_batch}
 
 
 def main():
+    global AMOUNT
     ap = argparse.ArgumentParser()
     ap.add_argument('--modes', default='loop,compose,batch')
     ap.add_argument('--rows', default='1,8,64,512,4096')
+    ap.add_argument('--amount', type=int, default=AMOUNT)
     ap.add_argument('--repeats', type=int, default=7)
     ap.add_argument('--out', default='')
     a = ap.parse_args()
+    AMOUNT = a.amount
     modes = [m for m in a.modes.split(',') if m]
     rows = [int(r) for r in a.rows.split(',')]
     P = model_ref.init_params(V, D, seed=20250301, bias_std=0.01)

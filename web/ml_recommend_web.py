@@ -22,3 +22,14 @@ def get_ml_recommend(cube_name, amount, root=ROOT, non_json=False,
                            print_cuts=False)                           # :50-64 (additions only)
     if not non_json:
         return output
+
+
+def get_ml_recommend_many(cube_names, amount, root=ROOT,
+                          model_dir='./ml_files/recommender', id_map='./ml_files/recommender_id_map.json'):
+    """get_ml_recommend in JSON mode for every cube of cube_names, scored in one batched call
+    (api.recommend_many): a list of the dicts get_ml_recommend returns, in the order given."""
+    int_to_card, card_to_int = api.load_id_map(id_map)
+    cubes_indices = [api.cube_indices_of(api.fetch_cube_list(name, root), card_to_int)
+                     for name in cube_names]
+    model = api.get_model(model_dir)
+    return api.recommend_many(model, cubes_indices, amount, int_to_card)
