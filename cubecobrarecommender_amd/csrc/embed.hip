@@ -12,9 +12,11 @@
 //   get an exact zero gradient, as TF's dense MatMul gradient gives).
 #include <algorithm>
 #include <cstdlib>
+#include <type_traits>
 
 #include "adam.hpp"
 #include "common.hpp"
+#include "tower_dw_dev.hpp"
 #include "xt.hpp"
 
 // build knobs (A/B builds: CCREC_EXTRA_FLAGS=-D..., a tagged library; the library reads no
@@ -828,15 +830,36 @@ constexpr int CS_REG_MAX = 512;   // (one 32-bit mask of reg k-steps per tile)
 // profiles/r06z_w1_reg_lds_ab.txt) nor each batch's rid reads / A bytes / LUT reads / MFMAs issued
 // phase by phase (neutral, profiles/r06g_w1_reg_pipe_ab.txt) beat the code below.)
 
-template <bool PK, int XWM, bool VEC, bool ADAM, bool REG = false>
+// DW: the tower weight gradients (tower_dw_dev.hpp, cc_tower_bwd_dw_direct's one-wave jobs) ride in
+// this launch.  Blocks [0, nw1) are the W1 blocks, mapped exactly as without riders; blocks
+// [nw1, nw1 + nr) are riders: wave w of rider b runs jobs 8 b + w, 8 b + w + 8 nr, ... in order and
+// returns — no LDS stage, no ticket, no barrier, nothing shared with the W1 blocks (the jobs read
+// only the backward chain's hpt / gpt images).  The W1 product is HBM-bound and leaves its CUs'
+// MFMA and issue slots idle; cs_plan's reserve mode keeps nr CUs free of W1 blocks for the riders.
+struct CsDw {
+  cctower::TowerP tp;
+  int nw1, nr, jobs;
+};
+struct CsNoDw {};
+
+template <bool PK, int XWM, bool VEC, bool ADAM, bool REG = false, bool DW = false>
 __global__ __launch_bounds__(CS_NT, 1) void embed_grad_cs_kernel(const bf16_t *__restrict__ gsrc, int V, int d, int R,
                                                             int RP, int tpc, uint32_t *xt,
                                                             float *__restrict__ grad,
                                                             float *__restrict__ bias_grad, uint32_t *tickets,
-                                                            CsAdam ad, CsReg rg) {
+                                                            CsAdam ad, CsReg rg,
+                                                            typename std::conditional<DW, CsDw, CsNoDw>::type dw) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   __shared__ int last;
   const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6, half = lane >> 5;
+  if constexpr (DW) {
+    if ((int)blockIdx.x >= dw.nw1) {  // a rider (block-uniform: before every barrier of the W1 path)
+      const int b = (int)blockIdx.x - dw.nw1;
+      for (int job = (CS_NT / 64) * b + w; job < dw.jobs; job += (CS_NT / 64) * dw.nr)
+        cctower::dw_packed_tile(dw.tp, job, lane);
+      return;
+    }
+  }
   const int nsl = d >> 5, cs = blockIdx.x % nsl, rc = blockIdx.x / nsl;
   const int RPE = (R + 63) & ~63, nk = RPE >> 4;
   const int XW = (R + 31) >> 5;  // words per xt row; the product runs over XWM words (zeros past XW)
@@ -1164,7 +1187,11 @@ __global__ __launch_bounds__(CS_NT, 1) void embed_grad_cs_kernel(const bf16_t *_
 }
 
 // launch geometry of cc_embed_grad_cs: 32-row tiles per chunk and the LDS size
-void cs_plan(int V, int d, int R, bool bias, int &tpc, int &nrc, size_t &lds, bool adam = false) {
+// reserve > 0 (riders): the chunks are made coarser until the W1 blocks leave `reserve` of the 256
+// CUs free — the fewest tiles per chunk (the most chunks nrc) with nrc nsl + reserve <= 256 that
+// still fit a block's 8 cs_tpw tiles; unchanged where the grid already leaves them free or no such
+// chunking exists.  Every 32-row tile is one wave's work whatever the chunking: the same bits.
+void cs_plan(int V, int d, int R, bool bias, int &tpc, int &nrc, size_t &lds, bool adam = false, int reserve = 0) {
   const int RPE = (R + 63) & ~63;
   const int NTL = (V + (bias ? 1 : 0) + 31) / 32;
   const int xwm = RPE / 32 <= 16 ? 16 : RPE / 32 <= 32 ? 32 : 64;  // the kernel's XWM
@@ -1177,6 +1204,13 @@ void cs_plan(int V, int d, int R, bool bias, int &tpc, int &nrc, size_t &lds, bo
   if (nrc * nsl > 256 && 256 % nsl == 0) nrc = (int)cdiv(nrc, 256 / nsl) * (256 / nsl);
   tpc = (int)cdiv(NTL, nrc);
   nrc = (int)cdiv(NTL, tpc);
+  if (reserve > 0 && nrc * nsl + reserve > 256 && (256 - reserve) / nsl >= 1) {
+    const int t2 = (int)cdiv(NTL, (256 - reserve) / nsl);
+    if (t2 <= (CS_NT / 64) * cs_tpw(xwm, adam)) {
+      tpc = t2;
+      nrc = (int)cdiv(NTL, tpc);
+    }
+  }
   lds = (size_t)2 * xwm * 1024 + cs_lut_bytes(xwm, adam) + (adam ? (size_t)(CS_NT / 64) * 32 * 36 * 4 : 0);
 }
 
@@ -1191,15 +1225,32 @@ extern "C" int32_t cc_embed_grad_cs_tickets(int32_t V, int32_t d, int32_t R) {
   return std::max(nrc, nrc_adam);
 }
 
-static int embed_grad_cs_launch(const void *dpre, int32_t packed, int32_t V, int32_t d, int32_t R, int32_t ld_t,
-                                uint32_t *xt_bits, float *grad, float *bias_grad, uint32_t *tickets,
-                                const CsAdam *ad, void *stream, const CsReg *rg = nullptr) {
+// the launch geometry of cc_embed_grad_cs_adam (n_riders == 0) / cc_embed_grad_cs_adam_dw: W1 row
+// chunks, 32-row tiles per chunk, the most tiles a wave takes (its register budget); returns the
+// W1 blocks (chunks x d / 32 column slices; the riders follow them), 0 for a shape it rejects
+extern "C" int32_t cc_embed_grad_cs_geometry(int32_t V, int32_t d, int32_t R, int32_t n_riders, int32_t *chunks,
+                                             int32_t *tiles_per_chunk, int32_t *tiles_per_wave) {
+  if (V <= 0 || d < 32 || d % 32 || R <= 0 || R > 2048 || n_riders < 0) return 0;
   int tpc, nrc;
   size_t lds;
-  cs_plan(V, d, R, bias_grad != nullptr, tpc, nrc, lds, ad != nullptr);
+  cs_plan(V, d, R, true, tpc, nrc, lds, true, n_riders);
+  const int RPE = (R + 63) & ~63;
+  if (chunks) *chunks = nrc;
+  if (tiles_per_chunk) *tiles_per_chunk = tpc;
+  if (tiles_per_wave) *tiles_per_wave = cs_tpw(RPE / 32 <= 16 ? 16 : RPE / 32 <= 32 ? 32 : 64, true);
+  return nrc * (d / 32);
+}
+
+static int embed_grad_cs_launch(const void *dpre, int32_t packed, int32_t V, int32_t d, int32_t R, int32_t ld_t,
+                                uint32_t *xt_bits, float *grad, float *bias_grad, uint32_t *tickets,
+                                const CsAdam *ad, void *stream, const CsReg *rg = nullptr, CsDw *dw = nullptr) {
+  int tpc, nrc;
+  size_t lds;
+  cs_plan(V, d, R, bias_grad != nullptr, tpc, nrc, lds, ad != nullptr, dw ? dw->nr : 0);
   if (rg) lds += (size_t)((rg->nreg + 511) & ~511) * 4;
   CC_REQUIRE(lds <= 160 * 1024 - 64, "cc_embed_grad_cs: R too large for the LDS stage");
-  const dim3 grid((unsigned)(nrc * (d / 32)));
+  if (dw) dw->nw1 = nrc * (d / 32);
+  const dim3 grid((unsigned)(nrc * (d / 32) + (dw ? dw->nr : 0)));
   const int xw = ((R + 63) & ~63) / 32;  // bit words per row in the product
   const bool vec = ((R + 31) / 32) % 4 == 0;  // xt rows 16-B aligned
   const CsAdam a = ad ? *ad : CsAdam{};
@@ -1207,12 +1258,23 @@ static int embed_grad_cs_launch(const void *dpre, int32_t packed, int32_t V, int
   hipStream_t s = as_stream(stream);
 #define CS_LAUNCH(PKV, XWMV, VECV, ADV)                                                                          \
   do {                                                                                                           \
+    if constexpr (ADV) {                                                                                         \
+      if (dw) {                                                                                                  \
+        if (rg)                                                                                                  \
+          hipLaunchKernelGGL((embed_grad_cs_kernel<PKV, XWMV, VECV, true, true, true>), grid, dim3(CS_NT), lds, s, \
+                             (const bf16_t *)dpre, V, d, R, ld_t, tpc, xt_bits, grad, bias_grad, tickets, a, r, *dw); \
+        else                                                                                                     \
+          hipLaunchKernelGGL((embed_grad_cs_kernel<PKV, XWMV, VECV, true, false, true>), grid, dim3(CS_NT), lds, s, \
+                             (const bf16_t *)dpre, V, d, R, ld_t, tpc, xt_bits, grad, bias_grad, tickets, a, r, *dw); \
+        break;                                                                                                   \
+      }                                                                                                          \
+    }                                                                                                            \
     if (rg)                                                                                                      \
       hipLaunchKernelGGL((embed_grad_cs_kernel<PKV, XWMV, VECV, ADV, true>), grid, dim3(CS_NT), lds, s,          \
-                         (const bf16_t *)dpre, V, d, R, ld_t, tpc, xt_bits, grad, bias_grad, tickets, a, r);     \
+                         (const bf16_t *)dpre, V, d, R, ld_t, tpc, xt_bits, grad, bias_grad, tickets, a, r, CsNoDw{}); \
     else                                                                                                         \
       hipLaunchKernelGGL((embed_grad_cs_kernel<PKV, XWMV, VECV, ADV>), grid, dim3(CS_NT), lds, s,                \
-                         (const bf16_t *)dpre, V, d, R, ld_t, tpc, xt_bits, grad, bias_grad, tickets, a, r);     \
+                         (const bf16_t *)dpre, V, d, R, ld_t, tpc, xt_bits, grad, bias_grad, tickets, a, r, CsNoDw{}); \
   } while (0)
 #define CS_LAUNCH2(XWMV, ADV)                                                                 \
   if (packed) {                                                                               \
@@ -1298,6 +1360,62 @@ extern "C" int cc_embed_grad_cs_adam_reg(const void *dpre, int32_t packed, int32
   const CsAdam ad{p, m, v, (bf16_t *)shadow, state, lr, beta1, beta2, eps};
   const CsReg rg{reg_idx, nreg, reg_k0, 0};
   return embed_grad_cs_launch(dpre, packed, V, d, R, ld_t, xt_bits, nullptr, bias_grad, tickets, &ad, stream, &rg);
+}
+
+// the rider forms: cc_tower_bwd_dw_direct's checks (tower.hip), the rider count, then the same launch
+static int cs_dw_args(const cc_tower_args *tower, int32_t n_riders, CsDw &dw, const char *who) {
+  CC_REQUIRE(n_riders >= 1 && n_riders <= 64, std::string(who) + ": n_riders in 1..64");
+  int rc = cctower::dw_rider_params(tower, dw.tp, dw.jobs, who);
+  if (rc) return rc;
+  dw.nr = n_riders;
+  dw.nw1 = 0;  // (set with the launch geometry)
+  return CC_OK;
+}
+
+extern "C" int cc_embed_grad_cs_adam_dw(const void *dpre, int32_t packed, int32_t V, int32_t d, int32_t R,
+                                        int32_t ld_t, uint32_t *xt_bits, float *bias_grad, uint32_t *tickets,
+                                        float *p, float *m, float *v, uint16_t *shadow, const int64_t *state,
+                                        float lr, float beta1, float beta2, float eps, const cc_tower_args *tower,
+                                        int32_t n_riders, void *stream) {
+  CC_REQUIRE(dpre && xt_bits && p && m && v && shadow && state, "cc_embed_grad_cs_adam_dw: null pointer");
+  CC_REQUIRE((((uintptr_t)p | (uintptr_t)m | (uintptr_t)v | (uintptr_t)bias_grad) & 15) == 0 &&
+                 ((uintptr_t)shadow & 7) == 0,
+             "cc_embed_grad_cs_adam_dw: p, m, v, bias_grad 16-B aligned, shadow 8-B aligned");
+  CC_REQUIRE(d % 32 == 0 && d >= 32 && d <= 4096, "cc_embed_grad_cs_adam_dw: d must be a multiple of 32");
+  CC_REQUIRE(V > 0 && R > 0 && R <= 2048, "cc_embed_grad_cs_adam_dw: V > 0, R in 1..2048");
+  CC_REQUIRE(ld_t % 64 == 0 && ld_t >= R && ((uintptr_t)dpre % 16) == 0,
+             "cc_embed_grad_cs_adam_dw: ld_t must be a multiple of 64 covering R, dPre1 image 16-B aligned");
+  CsDw dw;
+  int rc = cs_dw_args(tower, n_riders, dw, "cc_embed_grad_cs_adam_dw");
+  if (rc) return rc;
+  const CsAdam ad{p, m, v, (bf16_t *)shadow, state, lr, beta1, beta2, eps};
+  return embed_grad_cs_launch(dpre, packed, V, d, R, ld_t, xt_bits, nullptr, bias_grad, tickets, &ad, stream, nullptr,
+                              &dw);
+}
+
+extern "C" int cc_embed_grad_cs_adam_reg_dw(const void *dpre, int32_t packed, int32_t V, int32_t d, int32_t R,
+                                            int32_t ld_t, uint32_t *xt_bits, float *bias_grad, uint32_t *tickets,
+                                            float *p, float *m, float *v, uint16_t *shadow, const int64_t *state,
+                                            float lr, float beta1, float beta2, float eps, const int32_t *reg_idx,
+                                            int32_t nreg, int32_t reg_k0, const cc_tower_args *tower,
+                                            int32_t n_riders, void *stream) {
+  CC_REQUIRE(dpre && xt_bits && p && m && v && shadow && state, "cc_embed_grad_cs_adam_reg_dw: null pointer");
+  CC_REQUIRE((((uintptr_t)p | (uintptr_t)m | (uintptr_t)v | (uintptr_t)bias_grad) & 15) == 0 &&
+                 ((uintptr_t)shadow & 7) == 0,
+             "cc_embed_grad_cs_adam_reg_dw: p, m, v, bias_grad 16-B aligned, shadow 8-B aligned");
+  CC_REQUIRE(d % 32 == 0 && d >= 32 && d <= 4096, "cc_embed_grad_cs_adam_reg_dw: d must be a multiple of 32");
+  CC_REQUIRE(V > 0 && R > 0 && R <= 2048, "cc_embed_grad_cs_adam_reg_dw: V > 0, R in 1..2048");
+  CC_REQUIRE(ld_t % 64 == 0 && ld_t >= R && ((uintptr_t)dpre % 16) == 0,
+             "cc_embed_grad_cs_adam_reg_dw: ld_t must be a multiple of 64 covering R, dPre1 image 16-B aligned");
+  const char *e = cs_reg_check(reg_idx, nreg, reg_k0, R, ld_t);
+  CC_REQUIRE(!e, e);
+  CsDw dw;
+  int rc = cs_dw_args(tower, n_riders, dw, "cc_embed_grad_cs_adam_reg_dw");
+  if (rc) return rc;
+  const CsAdam ad{p, m, v, (bf16_t *)shadow, state, lr, beta1, beta2, eps};
+  const CsReg rg{reg_idx, nreg, reg_k0, 0};
+  return embed_grad_cs_launch(dpre, packed, V, d, R, ld_t, xt_bits, nullptr, bias_grad, tickets, &ad, stream, &rg,
+                              &dw);
 }
 
 extern "C" int cc_embed_gather_fwd_warm(int32_t dtype, const void *table, const float *bias, int32_t V,

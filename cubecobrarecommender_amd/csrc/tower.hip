@@ -16,6 +16,7 @@
 #include "common.hpp"
 #include "mx8.hpp"
 #include "noise_dev.hpp"
+#include "tower_dw_dev.hpp"
 #include "xt.hpp"
 
 // dev-only timing hook (tools/micro/tower_probe.hip defines it); compiled out of the library
@@ -23,46 +24,17 @@
 #define TOWER_PROBE(k)
 #endif
 
+using cctower::chain_dims;
+using cctower::dw_job;
+using cctower::DWP_U;
+using cctower::pack_off;
+using cctower::TowerP;
+
 namespace {
 
 constexpr int RB = 32;   // rows per block
 constexpr int NT = 256;  // 4 waves
 
-struct TowerP {
-  int d, B, R, maxw;
-  const void *w[9];
-  void *wt[9];
-  const float *b[9];
-  void *act[7];
-  void *act6t;
-  const void *gD3;
-  void *gact[5];
-  float *gpre1;
-  void *gpre1t;  // optional bf16 dPre1^T [d][ceil64(R)]
-  float *slab;
-  int64_t slab_elems;
-  float *gw[9];
-  float *gb[9];
-  const bf16_t *wpf[9];  // fragment-packed forward / backward weight images (cc_tower_args)
-  const bf16_t *wpb[9];
-  bf16_t *act6p, *act6tp;  // packed D3 operand images for cc_dec_bce_dw (fast forward only)
-  bf16_t *hpt[6], *gpt[6];  // packed transposed H_i / G_i images for the dW kernel (or null)
-  bf16_t *gpre1p;           // packed transposed dPre1 for cc_embed_grad_packed (or null)
-  const uint32_t *xb;       // x row bitmasks -> xt (fast forward's extra blocks; or null)
-  uint32_t *xt;
-  int xt_V, xt_rows;
-  uint8_t *d3q, *d3qs, *d3tq, *d3tqs;  // D3's MX-FP8 operand images (config 5; wide forward only, or null)
-  const uint32_t *yb;       // y row bitmasks [B][y_VW] -> yimg (fast forward's extra blocks; or null)
-  uint32_t *yimg;
-  int y_VW;
-  bool packed, dwpacked;
-};
-
-__host__ __device__ inline void chain_dims(int d, int i, int &K, int &N) {
-  // K: d, 256, 128, 64, 128, 256;  N: 256, 128, 64, 128, 256, d  (no arrays: no scratch)
-  K = i == 0 ? d : i == 1 ? 256 : i == 2 ? 128 : i == 3 ? 64 : i == 4 ? 128 : 256;
-  N = i == 0 ? 256 : i == 1 ? 128 : i == 2 ? 64 : i == 3 ? 128 : i == 4 ? 256 : d;
-}
 __host__ __device__ inline int64_t slab_off(int d, int i) {  // chain layer i (0..5): kernel, bias
   int64_t o = 0;
   for (int j = 0; j < i; ++j) {
@@ -345,11 +317,6 @@ __device__ __forceinline__ void issue_frags_packed(Frags &F, const bf16_t *__res
   for (int j = 0; j < FB; ++j)
     if (16 * j < red) F.f[j] = *reinterpret_cast<const bf16x8_t *>(base + j * 512);
 }
-// packed-image element offset of fragment (t, j), lane, element e
-__device__ __forceinline__ int64_t pack_off(int t, int j, int lane, int red) {
-  return (((int64_t)t * (red / 16) + j) * 64 + lane) * 8;
-}
-
 // 32 rows x W (bf16, W <= 256) of a [R][W] activation into registers: issue now, store to LDS later
 typedef __attribute__((ext_vector_type(4))) uint32_t u32v4;  // staging registers (HIP's uint4
                                                               // struct would be spilled to scratch)
@@ -1019,26 +986,6 @@ __global__ __launch_bounds__(NT) void tower_dw_kernel(TowerP p) {
 // first k-block also sum G's columns: the bias gradient.  Replaces tower_dw + tower_reduce.
 constexpr int DW_NT = 256;
 
-__device__ __forceinline__ bool dw_job(const TowerP &p, int bid, int &l, int &i, int &k0, int &n0,
-                                       int &row0, int &nrows) {
-  const int L = p.R > p.B ? 9 : 6;
-  for (l = 0; l < L; ++l) {
-    i = l < 6 ? l : l - 3;
-    int K, N;
-    chain_dims(p.d, i, K, N);
-    const int tn = N / 32, nt = (K / 32) * tn;
-    if (bid < nt) {
-      k0 = 32 * (bid / tn);
-      n0 = 32 * (bid % tn);
-      row0 = l < 6 ? 0 : p.B;
-      nrows = l < 3 ? p.R : (l < 6 ? p.B : p.R - p.B);   // reg branch: rows [B, R)
-      return true;
-    }
-    bid -= nt;
-  }
-  return false;
-}
-
 __global__ __launch_bounds__(DW_NT) void tower_dw_tiled_kernel(TowerP p, int rpw) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   int l, i, k0, n0, row0, nrows;
@@ -1100,58 +1047,10 @@ __global__ __launch_bounds__(DW_NT) void tower_dw_tiled_kernel(TowerP p, int rpw
                                 pcs[96 + threadIdx.x];
 }
 
-// dW from the packed transposed images: one wave per 32x32 tile of one layer, dW[k0.., n0..] =
-// sum over the layer's rows of H^T G as a chain of v_mfma_f32_32x32x16_bf16 whose A / B fragments
-// are whole 1 KB runs of hpt / gpt (no LDS staging, no cross-wave reduce); db from the same B
-// fragments on the k0 == 0 tiles.  Rows in order: deterministic.
-constexpr int DWP_U = 8;  // fragment pairs in flight per lane
+// dW from the packed transposed images: one wave per 32 x 32 tile of one layer (tower_dw_dev.hpp:
+// the same job also rides in the W1-gradient launch, cc_embed_grad_cs_adam_dw)
 __global__ __launch_bounds__(64) void tower_dw_packed_kernel(TowerP p) {
-  int l, i, k0, n0, row0, nrows;
-  if (!dw_job(p, blockIdx.x, l, i, k0, n0, row0, nrows)) return;
-  int K, N;
-  chain_dims(p.d, i, K, N);
-  const int lane = threadIdx.x, half = lane >> 5;
-  const int R = p.R, j0 = row0 / 16, nj = nrows / 16;
-  const bf16_t *ha = p.hpt[i] + pack_off(k0 / 32, j0, lane, R);
-  const bf16_t *gb = p.gpt[i] + pack_off(n0 / 32, j0, lane, R);
-  f32x16_t acc;
-#pragma unroll
-  for (int r = 0; r < 16; ++r) acc[r] = 0.f;
-  float cs = 0.f;
-  const bool bias = k0 == 0;
-  int j = 0;
-  for (; j + DWP_U <= nj; j += DWP_U) {
-    bf16x8_t a[DWP_U], b[DWP_U];
-#pragma unroll
-    for (int u = 0; u < DWP_U; ++u) {
-      a[u] = *reinterpret_cast<const bf16x8_t *>(ha + (j + u) * 512);
-      b[u] = *reinterpret_cast<const bf16x8_t *>(gb + (j + u) * 512);
-    }
-#pragma unroll
-    for (int u = 0; u < DWP_U; ++u) {
-      acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[u], b[u], acc, 0, 0, 0);
-      if (bias) {
-#pragma unroll
-        for (int e = 0; e < 8; ++e) cs += (float)b[u][e];
-      }
-    }
-  }
-  for (; j < nj; ++j) {
-    const bf16x8_t a = *reinterpret_cast<const bf16x8_t *>(ha + j * 512);
-    const bf16x8_t b = *reinterpret_cast<const bf16x8_t *>(gb + j * 512);
-    acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, b, acc, 0, 0, 0);
-    if (bias) {
-#pragma unroll
-      for (int e = 0; e < 8; ++e) cs += (float)b[e];
-    }
-  }
-  float *gw = p.gw[l] + (int64_t)(k0 + 4 * half) * N + n0 + (lane & 31);
-#pragma unroll
-  for (int r = 0; r < 16; ++r) gw[(int64_t)((r & 3) + 8 * (r >> 2)) * N] = acc[r];
-  if (bias) {
-    cs += __shfl_xor(cs, 32);
-    if (half == 0) p.gb[l][n0 + lane] = cs;
-  }
+  cctower::dw_packed_tile(p, blockIdx.x, threadIdx.x);
 }
 
 // Row-split form for tall layers (full-mode regulariser: ~22k rows per chain): job (tile, split s)
@@ -1582,28 +1481,43 @@ extern "C" int cc_tower_reduce(const cc_tower_args *t, void *stream) {
   return CC_OK;
 }
 
-extern "C" int cc_tower_bwd_dw_direct(const cc_tower_args *t, void *stream) {
-  TowerP p;
+// cc_tower_bwd_dw_direct's arguments: the checks, the job count and whether the packed form splits
+// a tall chain by rows (S > 1) — shared with the launches that host the jobs (dw_rider_params)
+static int dw_direct_params(const cc_tower_args *t, TowerP &p, int &jobs, int &S, const std::string &who) {
   int rc = make_params(t, p);
   if (rc) return rc;
-  CC_REQUIRE(t->dtype == CC_BF16, "cc_tower_bwd_dw_direct: bf16 only");
-  CC_REQUIRE(t->gD3, "cc_tower_bwd_dw_direct: null gD3");
-  for (int a = 0; a < 5; ++a) CC_REQUIRE(t->gact[a], "cc_tower_bwd_dw_direct: null gact");
-  for (int l = 0; l < (t->R > t->B ? 9 : 6); ++l)
-    CC_REQUIRE(t->gw[l] && t->gb[l], "cc_tower_bwd_dw_direct: null gw/gb");
+  CC_REQUIRE(t->dtype == CC_BF16, who + ": bf16 only");
+  CC_REQUIRE(t->gD3, who + ": null gD3");
+  for (int a = 0; a < 5; ++a) CC_REQUIRE(t->gact[a], who + ": null gact");
+  for (int l = 0; l < (t->R > t->B ? 9 : 6); ++l) CC_REQUIRE(t->gw[l] && t->gb[l], who + ": null gw/gb");
+  jobs = cctower::dw_jobs(t->d, t->B, t->R);
+  // tall chains (full-mode regulariser rows): split the rows, S partials per tile in the slab
+  S = std::min(16, std::max(1, t->R / 1024));
+  if (!(p.dwpacked && S > 1 && p.slab && (int64_t)jobs * S * DWS_STRIDE <= (int64_t)(t->R / RB) * p.slab_elems)) S = 1;
+  return CC_OK;
+}
+
+int cctower::dw_rider_params(const cc_tower_args *t, TowerP &p, int &jobs, const char *who) {
+  int S;
+  int rc = dw_direct_params(t, p, jobs, S, who);
+  if (rc) return rc;
+  CC_REQUIRE(p.dwpacked, std::string(who) + ": needs the packed transposed hpt / gpt images (16-B aligned, B and R "
+                                            "multiples of 16) of the bf16 fast / wide chains");
+  CC_REQUIRE(S == 1, std::string(who) + ": tall chain (its dW is split by rows): run cc_tower_bwd_dw_direct and the "
+                                        "W1 gradient as two launches");
+  return CC_OK;
+}
+
+extern "C" int cc_tower_bwd_dw_direct(const cc_tower_args *t, void *stream) {
+  TowerP p;
+  int jobs, S;
+  int rc = dw_direct_params(t, p, jobs, S, "cc_tower_bwd_dw_direct");
+  if (rc) return rc;
   const int rmax = t->R > t->B ? t->R : t->B;
   const int rpw = ((rmax + 3) / 4 + 15) / 16 * 16;
   const size_t lds = std::max((size_t)4 * 2 * 32 * (rpw + 8) * 2, (size_t)(4 * 32 * 33 + 4 * 32) * 4);
-  int jobs = 0;
-  for (int l = 0; l < (t->R > t->B ? 9 : 6); ++l) {
-    int K, N;
-    chain_dims(t->d, l < 6 ? l : l - 3, K, N);
-    jobs += (K / 32) * (N / 32);
-  }
   if (p.dwpacked) {  // the forward / backward chains wrote the packed transposed H_i / G_i
-    // tall chains (full-mode regulariser rows): split the rows, S partials per tile in the slab
-    const int S = std::min(16, std::max(1, t->R / 1024));
-    if (S > 1 && p.slab && (int64_t)jobs * S * DWS_STRIDE <= (int64_t)(t->R / RB) * p.slab_elems) {
+    if (S > 1) {  // a tall chain, row-split
       hipLaunchKernelGGL(tower_dw_packed_split_kernel, dim3(jobs, S), dim3(64), 0, as_stream(stream), p, S, p.slab);
       CC_LAUNCH_CHECK("tower_dw_packed_split_kernel");
       hipLaunchKernelGGL(tower_dw_split_reduce_kernel, dim3(jobs), dim3(64), 0, as_stream(stream), p, S, p.slab);

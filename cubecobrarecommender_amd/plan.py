@@ -146,6 +146,7 @@ class StepPlan:
     rest_ranges: Optional[Tuple[Range, ...]]   # ... and what the Adam launch keeps
     wo_range: Optional[Range]
     f_in_tower: bool               # the next step's F in the tower backward launch
+    dw_in_w1: int                  # > 0: the tower dW jobs ride in the W1-gradient launch, on this many riders
     # data parallel (zero.py)
     early_reg_out: bool            # both output layers are one early bucket
     dp_defer_out_ok: bool          # the output layers' all-gather may wait for the next step's head
@@ -306,6 +307,16 @@ def plan_step(cfg, cdf=None, data_reg_rows=None):
     # the next step's F in the tower backward launch: one process with F prefetched and the xt bits
     # made by the tower forward's transpose (so F sets none the W1 gradient still reads)
     f_in_tower = bool(cfg.f_in_tower and adam_packs and xt_in_tower and not full_reg)
+    # the tower weight gradients as rider workgroups of the W1 gradient + Adam launch
+    # (cc_embed_grad_cs_adam_dw) instead of their own launch between the backward chain and it:
+    # with tower_dw == 'direct' from the packed hpt / gpt images (pack) only, and neither the
+    # full-mode regulariser nor any chain of 2048 rows or more (tower.hip splits a tall chain's dW
+    # by rows: its own two launches).  The value is the rider count (cfg.dw_in_w1 < 0: measured
+    # per mode — 16 riders BCE only, 147.2 -> 143.0 us per step; with the sampled regulariser the
+    # 1024-row chains' jobs outlast the W1 product on the 16 - 24 CUs it can spare: off).
+    riders = int(cfg.dw_in_w1) if cfg.dw_in_w1 >= 0 else (0 if use_reg else 16)
+    dw_in_w1 = riders if fuse_w1 and pack and not full_reg and R < 2048 else 0
+    assert 0 <= dw_in_w1 <= 64, 'dw_in_w1: 0 (off) or 1..64 rider workgroups'
     # zero.py: the bf16 / fp8 layout's output layers are one early bucket (its exchange waits for
     # the regulariser branch too); it may defer their all-gather to the next step's head when
     # nothing between this step's Adam and the next D1 launch reads their shadow (the fused kernels
@@ -325,7 +336,8 @@ def plan_step(cfg, cdf=None, data_reg_rows=None):
         splits_reg=splits_reg, dx_kernels=dx_kernels, prefetch=prefetch, prefetch_dp=prefetch_dp,
         xt_in_gather=xt_in_gather, has_x_bits=xt_in_gather, xt_in_tower=xt_in_tower, has_y_img=has_y_img,
         adam_packs=adam_packs, w1_off=w1_off, fuse_w1=fuse_w1, wo_ranges=wo_ranges, rest_ranges=rest_ranges,
-        wo_range=wo_ranges[0] if wo_ranges else None, f_in_tower=f_in_tower, early_reg_out=early_reg_out,
+        wo_range=wo_ranges[0] if wo_ranges else None, f_in_tower=f_in_tower, dw_in_w1=dw_in_w1,
+        early_reg_out=early_reg_out,
         dp_defer_out_ok=dp_defer_out_ok,
         bucket_hook_names=tuple(f'w1_{i}' for i in range(nchunks)),
         f_bucket_name=f'w1_{nchunks - 1}' if layout.group_biases else 'towers_e1')

@@ -77,6 +77,10 @@ class TrainConfig:
     f_in_tower: bool = False       # one process, bf16 fast chains: the NEXT step's F as extra workgroups
     #                                of the tower backward launch (cc_tower_bwd_chain_noise; every batch
     #                                buffer F writes is free by then) instead of the Adam launch (bench.py)
+    dw_in_w1: int = -1             # with fuse_w1_adam and the packed tower images: the tower weight gradients
+    #                                as this many rider workgroups of the W1 gradient + Adam launch
+    #                                (cc_embed_grad_cs_adam_dw; bit-identical), 0: their own launch (< 0:
+    #                                measured per mode — 16 BCE only, 0 with the regulariser)
     wo_tower_frac: float = -1.0    # ... on this trailing fraction of each; the rest stays in the Adam + F
     #                                launch (< 0: measured per mode — 0.6 BCE only, 0.55 with the
     #                                sampled regulariser; bench.py --wo-tower-frac sweeps)
@@ -172,6 +176,7 @@ class Trainer:
                    'embed_mfma', 'tsplits', 'dx_glds', 'fused_out', 'dz1_ld', 'fused_reg', 'd3q_in_tower',
                    'mx8_bce_q', 'reg_logits_paired', 'splits', 'splits_reg', 'prefetch', 'prefetch_dp',
                    'xt_in_gather', 'xt_in_tower', 'adam_packs', 'w1_off', 'fuse_w1', 'wo_range', 'f_in_tower',
+                   'dw_in_w1',
                    'early_reg_out')
 
     def __init__(self, cfg: TrainConfig, data: DeviceDataset, params_flat=None, device='cuda'):
@@ -972,7 +977,8 @@ class Trainer:
                 L.call('cc_tower_bwd_chain', L.C.byref(self.targs), s)
             t()
             if self.plan.tower_dw == 'direct':   # bf16: dW straight from the packed images
-                L.call('cc_tower_bwd_dw_direct', L.C.byref(self.targs), s)
+                if not self.dw_in_w1:            # (else: riders of the W1 gradient + Adam launch below)
+                    L.call('cc_tower_bwd_dw_direct', L.C.byref(self.targs), s)
             else:                                # per-block dW slabs + their reduce
                 L.call('cc_tower_bwd_dw', L.C.byref(self.targs), s)
                 L.call('cc_tower_reduce', L.C.byref(self.targs), s)
@@ -986,16 +992,18 @@ class Trainer:
         if self.fuse_w1:   # column slices + TF Adam on W1 in the epilogue
             cfg_ = self.cfg
             src, pk = (self.gpre1p, 1) if self.gpre1p is not None else (self.gPre1T, 0)
-            if self.reg_by_index:   # + the reg rows by index (rows B .. of the dPre1 image)
-                L.call('cc_embed_grad_cs_adam_reg', L.ptr(src), pk, V, d, XR, self.RP, L.ptr(self.xt_bits),
-                       self.gp('encoder/encoded_1/bias'), self._eg_tk(), L.ptr(self.params), L.ptr(self.m),
-                       L.ptr(self.v), L.ptr(self.shadow), L.ptr(self.state), cfg_.lr, cfg_.beta1, cfg_.beta2,
-                       cfg_.eps, L.ptr(self.reg_idx), self.Breg, cfg.batch_size // 16, s)
+            w1 = (L.ptr(src), pk, V, d, XR, self.RP, L.ptr(self.xt_bits), self.gp('encoder/encoded_1/bias'),
+                  self._eg_tk(), L.ptr(self.params), L.ptr(self.m), L.ptr(self.v), L.ptr(self.shadow),
+                  L.ptr(self.state), cfg_.lr, cfg_.beta1, cfg_.beta2, cfg_.eps)
+            if self.dw_in_w1 and self.reg_by_index:   # + the tower dW jobs on rider workgroups
+                L.call('cc_embed_grad_cs_adam_reg_dw', *w1, L.ptr(self.reg_idx), self.Breg, cfg.batch_size // 16,
+                       L.C.byref(self.targs), self.dw_in_w1, s)
+            elif self.dw_in_w1:
+                L.call('cc_embed_grad_cs_adam_dw', *w1, L.C.byref(self.targs), self.dw_in_w1, s)
+            elif self.reg_by_index:   # + the reg rows by index (rows B .. of the dPre1 image)
+                L.call('cc_embed_grad_cs_adam_reg', *w1, L.ptr(self.reg_idx), self.Breg, cfg.batch_size // 16, s)
             else:
-                L.call('cc_embed_grad_cs_adam', L.ptr(src), pk, V, d, XR, self.RP, L.ptr(self.xt_bits),
-                       self.gp('encoder/encoded_1/bias'), self._eg_tk(), L.ptr(self.params), L.ptr(self.m),
-                       L.ptr(self.v), L.ptr(self.shadow), L.ptr(self.state), cfg_.lr, cfg_.beta1, cfg_.beta2,
-                       cfg_.eps, s)
+                L.call('cc_embed_grad_cs_adam', *w1, s)
         elif self.eg_tickets is not None:   # column slices (cc_embed_grad_cs), from the packed image or dPre1^T
             src, pk = (self.gpre1p, 1) if self.gpre1p is not None else (self.gPre1T, 0)
             # data parallel: W1's row chunks one launch each (the bias row with the last), each

@@ -245,6 +245,29 @@ int cc_embed_grad_cs_adam_reg(const void *dpre, int32_t packed, int32_t V, int32
                               float *v, uint16_t *shadow, const int64_t *state, float lr, float beta1,
                               float beta2, float eps, const int32_t *reg_idx, int32_t nreg, int32_t reg_k0,
                               void *stream);
+/* cc_embed_grad_cs_adam / cc_embed_grad_cs_adam_reg with the tower weight gradients of
+ * cc_tower_bwd_dw_direct(tower) in the same launch: n_riders (1..64) extra workgroups after the W1
+ * workgroups run its one-wave-per-tile jobs (the W1 product is HBM-bound; the jobs need only the
+ * backward chain's hpt / gpt images, nothing of this product), and the W1 row chunks are made
+ * coarser so that the W1 workgroups leave n_riders of the 256 CUs free where that fits.  Every
+ * result is bit-identical to cc_tower_bwd_dw_direct followed by the plain call (a W1 tile and a dW
+ * job are each one wave's work, whatever the launch).  tower: as for cc_tower_bwd_dw_direct, with
+ * the packed hpt / gpt images; a tall chain whose dW that call splits by rows (R >= 2048 with a
+ * slab) is refused — run the two launches.  The tickets of cc_embed_grad_cs_tickets cover it.
+ * cc_embed_grad_cs_geometry: the launch geometry for n_riders (0: the plain call) — W1 row chunks,
+ * 32-row tiles per chunk, the most tiles one wave takes; returns the W1 workgroups (0: bad shape). */
+struct cc_tower_args;
+int cc_embed_grad_cs_adam_dw(const void *dpre, int32_t packed, int32_t V, int32_t d, int32_t R, int32_t ld_t,
+                             uint32_t *xt_bits, float *bias_grad, uint32_t *tickets, float *p, float *m, float *v,
+                             uint16_t *shadow, const int64_t *state, float lr, float beta1, float beta2, float eps,
+                             const struct cc_tower_args *tower, int32_t n_riders, void *stream);
+int cc_embed_grad_cs_adam_reg_dw(const void *dpre, int32_t packed, int32_t V, int32_t d, int32_t R, int32_t ld_t,
+                                 uint32_t *xt_bits, float *bias_grad, uint32_t *tickets, float *p, float *m,
+                                 float *v, uint16_t *shadow, const int64_t *state, float lr, float beta1,
+                                 float beta2, float eps, const int32_t *reg_idx, int32_t nreg, int32_t reg_k0,
+                                 const struct cc_tower_args *tower, int32_t n_riders, void *stream);
+int32_t cc_embed_grad_cs_geometry(int32_t V, int32_t d, int32_t R, int32_t n_riders, int32_t *chunks,
+                                  int32_t *tiles_per_chunk, int32_t *tiles_per_wave);
 /* Full-mode regulariser (all |V| one-hot identity rows, README.md:27 KL(M, D2(E(I)))): the rows'
  * W1 gradient is dPre1 itself — grad[lo + r] += round(dpre[r]) for r < n and, with bias_grad,
  * bias_grad += sum_r round(dpre[r]) in a fixed order; round = bf16 RNE for dtype CC_BF16 (the
