@@ -83,6 +83,27 @@ class AdamPack(C.Structure):
 
 _P, _I32, _I64, _F32, _F64, _SZ = C.c_void_p, C.c_int32, C.c_int64, C.c_float, C.c_double, C.c_size_t
 
+# The six entries of the column-slice W1 gradient (cc_embed_grad_cs*): a form is (adam, reg, riders),
+# its name the suffixes in that order, its arguments the pieces below in the order of
+# _w1_grad_args — callers (trainer.py) append the same pieces' values.
+_W1 = [_P, _I32, _I32, _I32, _I32, _I32, _P]                  # dpre, packed, V, d, R, ld_t, xt_bits
+_W1_ADAM = [_P, _P, _P, _P, _P, _F32, _F32, _F32, _F32]       # p, m, v, shadow, state, lr, beta1, beta2, eps
+_W1_REG = [_P, _I32, _I32]                                    # reg_idx, nreg, reg_k0
+_W1_DW = [C.POINTER(TowerArgs), _I32]                         # tower, n_riders
+W1_GRAD_FORMS = [(False, False, False), (True, False, False), (False, True, False), (True, True, False),
+                 (True, False, True), (True, True, True)]     # (riders come with Adam only)
+
+
+def w1_grad_name(adam=False, reg=False, riders=False):
+    return 'cc_embed_grad_cs' + ('_adam' if adam else '') + ('_reg' if reg else '') + ('_dw' if riders else '')
+
+
+def _w1_grad_args(adam, reg, riders):
+    out = [_P, _P] if adam else [_P, _P, _P]                  # [grad: stored without Adam only], bias_grad, tickets
+    tail = _W1_REG + ([] if adam else [_I32]) if reg else []  # (card0: a row chunk's first card, without Adam)
+    return _W1 + out + (_W1_ADAM if adam else []) + tail + (_W1_DW if riders else []) + [_P]   # ..., stream
+
+
 # name -> (restype, argtypes); every symbol include/ccrec.h declares
 SIGNATURES = {
     'cc_abi_version': (C.c_int, []),
@@ -151,18 +172,8 @@ SIGNATURES = {
     'cc_similar_ws_size': (_SZ, [_I32]),
     'cc_similar_cards': (C.c_int, [_P, _I32, _I32, _I32, _I32, _P, _P, _P, _P, _P]),
     'cc_embed_grad_packed': (C.c_int, [_P, _I32, _I32, _I32, _I32, _P, _P, _P, _P]),
-    'cc_embed_grad_cs': (C.c_int, [_P, _I32, _I32, _I32, _I32, _I32, _P, _P, _P, _P, _P]),
+    **{w1_grad_name(*form): (C.c_int, _w1_grad_args(*form)) for form in W1_GRAD_FORMS},
     'cc_embed_grad_cs_tickets': (_I32, [_I32, _I32, _I32]),
-    'cc_embed_grad_cs_adam': (C.c_int, [_P, _I32, _I32, _I32, _I32, _I32, _P, _P, _P, _P, _P, _P, _P, _P,
-                                        _F32, _F32, _F32, _F32, _P]),
-    'cc_embed_grad_cs_reg': (C.c_int, [_P, _I32, _I32, _I32, _I32, _I32, _P, _P, _P, _P, _P, _I32, _I32, _I32, _P]),
-    'cc_embed_grad_cs_adam_reg': (C.c_int, [_P, _I32, _I32, _I32, _I32, _I32, _P, _P, _P, _P, _P, _P, _P, _P,
-                                            _F32, _F32, _F32, _F32, _P, _I32, _I32, _P]),
-    'cc_embed_grad_cs_adam_dw': (C.c_int, [_P, _I32, _I32, _I32, _I32, _I32, _P, _P, _P, _P, _P, _P, _P, _P,
-                                           _F32, _F32, _F32, _F32, C.POINTER(TowerArgs), _I32, _P]),
-    'cc_embed_grad_cs_adam_reg_dw': (C.c_int, [_P, _I32, _I32, _I32, _I32, _I32, _P, _P, _P, _P, _P, _P, _P, _P,
-                                               _F32, _F32, _F32, _F32, _P, _I32, _I32, C.POINTER(TowerArgs), _I32,
-                                               _P]),
     'cc_embed_grad_cs_geometry': (_I32, [_I32, _I32, _I32, _I32, _P, _P, _P]),
     'cc_embed_identity_ws': (_SZ, [_I32, _I32]),
     'cc_embed_identity_add': (C.c_int, [_I32, _P, _I32, _I32, _I32, _P, _P, _P, _P]),

@@ -774,6 +774,26 @@ constexpr int cs_tpw(int xwm, bool adam = false) {  // tiles per wave (registers
 // epilogue's re-layout tiles, R > 1024): 2-way bank conflicts at 8 copies
 constexpr int cs_lut_copies(int xwm, bool adam) { return xwm <= 16 ? 16 : xwm <= 32 ? (adam ? 8 : 16) : 4; }
 constexpr int cs_lut_bytes(int xwm, bool adam) { return 256 * 16 * cs_lut_copies(xwm, adam); }
+// R -> the kernel's XWM: the bit words per row the product runs over (ceil64(R) rows, zeros past R)
+constexpr int cs_xwm(int R) {
+  const int xw = ((R + 63) & ~63) / 32;
+  return xw <= 16 ? 16 : xw <= 32 ? 32 : 64;
+}
+// the block's dynamic LDS, byte offsets (the kernel's pointers and the host's size: one layout): the
+// B slice (2 XWM fragments of 1 KB, fragment j at (j * 64 + lane) * 8), the LUT ([256 values][copies]
+// x 16 B), ADAM: a 32 x 36-float re-layout tile per wave, REG: the reg rows' cards, padded with -1
+// to a multiple of 512 entries
+constexpr int CS_LDS_MAX = 160 * 1024 - 64;
+struct CsLds { int bs, lut, tx, rl, total; };
+constexpr CsLds cs_lds(int xwm, bool adam, int nreg = 0) {
+  const int lut = 2 * xwm * 1024, tx = lut + cs_lut_bytes(xwm, adam);
+  const int rl = tx + (adam ? (CS_NT / 64) * 32 * 36 * 4 : 0);
+  return CsLds{0, lut, tx, rl, rl + ((nreg + 511) & ~511) * 4};
+}
+// no Adam instance at XWM = 64 (1024 < R): 131072 + 16384 + 36864 = 184320 bytes; the launcher's
+// LDS check turns those shapes away before the selection
+static_assert(cs_lds(64, true).total > CS_LDS_MAX && cs_lds(32, true, 512).total <= CS_LDS_MAX &&
+              cs_lds(64, false, 512).total <= CS_LDS_MAX, "which instances fit the LDS");
 __device__ __forceinline__ uint4 byte_bf16(uint32_t e) {  // 8 bits -> 8 bf16 of 1.0 / 0.0
   uint32_t w[4];
 #pragma unroll
@@ -869,11 +889,11 @@ __global__ __launch_bounds__(CS_NT, 1) void embed_grad_cs_kernel(const bf16_t *_
   const int v0 = 32 * t0;
   EG_PROBE(0);
   constexpr int LC = cs_lut_copies(XWM, ADAM);
-  bf16_t *Bs = reinterpret_cast<bf16_t *>(smem);                  // fragment j at (j * 64 + lane) * 8
-  unsigned char *lut = smem + (size_t)2 * XWM * 1024;             // [256 values][16 copies] x 16 B
-  float *tx = reinterpret_cast<float *>(lut + cs_lut_bytes(XWM, ADAM));  // ADAM: per-wave 32 x 36 tiles
-  // REG: the reg rows' cards, padded with -1 to a multiple of 512 entries
-  int32_t *rl = reinterpret_cast<int32_t *>(reinterpret_cast<unsigned char *>(tx) + (ADAM ? (CS_NT / 64) * 32 * 36 * 4 : 0));
+  constexpr CsLds LO = cs_lds(XWM, ADAM);
+  bf16_t *Bs = reinterpret_cast<bf16_t *>(smem + LO.bs);
+  unsigned char *lut = smem + LO.lut;
+  float *tx = reinterpret_cast<float *>(smem + LO.tx);    // (ADAM)
+  int32_t *rl = reinterpret_cast<int32_t *>(smem + LO.rl);  // (REG)
   // ---- every global read first: the bit words of all the wave's tiles (wave w takes tiles w,
   // w + 8, ... of the chunk; a lane holds its row's XWM words per tile), then the B slice and LUT
   // (every global load below is unconditional — clamped address, then a select — so the
@@ -1186,16 +1206,14 @@ __global__ __launch_bounds__(CS_NT, 1) void embed_grad_cs_kernel(const bf16_t *_
   EG_PROBE(15);
 }
 
-// launch geometry of cc_embed_grad_cs: 32-row tiles per chunk and the LDS size
+// launch geometry of cc_embed_grad_cs: the row chunks and their 32-row tiles
 // reserve > 0 (riders): the chunks are made coarser until the W1 blocks leave `reserve` of the 256
 // CUs free — the fewest tiles per chunk (the most chunks nrc) with nrc nsl + reserve <= 256 that
 // still fit a block's 8 cs_tpw tiles; unchanged where the grid already leaves them free or no such
 // chunking exists.  Every 32-row tile is one wave's work whatever the chunking: the same bits.
-void cs_plan(int V, int d, int R, bool bias, int &tpc, int &nrc, size_t &lds, bool adam = false, int reserve = 0) {
-  const int RPE = (R + 63) & ~63;
+void cs_plan(int V, int d, int R, bool bias, int &tpc, int &nrc, bool adam = false, int reserve = 0) {
   const int NTL = (V + (bias ? 1 : 0) + 31) / 32;
-  const int xwm = RPE / 32 <= 16 ? 16 : RPE / 32 <= 32 ? 32 : 64;  // the kernel's XWM
-  const int nsl = d / 32;
+  const int xwm = cs_xwm(R), nsl = d / 32;
   // ~one block per CU (the slice is staged once per block), at most cs_tpw tiles per wave
   nrc = std::max(std::max(1, std::min(NTL, 256 / nsl)), (int)cdiv(NTL, (CS_NT / 64) * cs_tpw(xwm, adam)));
   // more blocks than CUs (d = 1024: 29 chunks x 32 slices = 928): whole rounds of 256 blocks, so
@@ -1211,7 +1229,6 @@ void cs_plan(int V, int d, int R, bool bias, int &tpc, int &nrc, size_t &lds, bo
       nrc = (int)cdiv(NTL, tpc);
     }
   }
-  lds = (size_t)2 * xwm * 1024 + cs_lut_bytes(xwm, adam) + (adam ? (size_t)(CS_NT / 64) * 32 * 36 * 4 : 0);
 }
 
 }  // namespace
@@ -1219,9 +1236,8 @@ void cs_plan(int V, int d, int R, bool bias, int &tpc, int &nrc, size_t &lds, bo
 extern "C" int32_t cc_embed_grad_cs_tickets(int32_t V, int32_t d, int32_t R) {
   if (V <= 0 || d < 32 || R <= 0) return 0;
   int tpc, nrc, nrc_adam;
-  size_t lds;
-  cs_plan(V, d, R, true, tpc, nrc, lds);
-  cs_plan(V, d, R, true, tpc, nrc_adam, lds, true);  // (the Adam instance may chunk finer)
+  cs_plan(V, d, R, true, tpc, nrc);
+  cs_plan(V, d, R, true, tpc, nrc_adam, true);  // (the Adam instance may chunk finer)
   return std::max(nrc, nrc_adam);
 }
 
@@ -1232,114 +1248,130 @@ extern "C" int32_t cc_embed_grad_cs_geometry(int32_t V, int32_t d, int32_t R, in
                                              int32_t *tiles_per_chunk, int32_t *tiles_per_wave) {
   if (V <= 0 || d < 32 || d % 32 || R <= 0 || R > 2048 || n_riders < 0) return 0;
   int tpc, nrc;
-  size_t lds;
-  cs_plan(V, d, R, true, tpc, nrc, lds, true, n_riders);
-  const int RPE = (R + 63) & ~63;
+  cs_plan(V, d, R, true, tpc, nrc, true, n_riders);
   if (chunks) *chunks = nrc;
   if (tiles_per_chunk) *tiles_per_chunk = tpc;
-  if (tiles_per_wave) *tiles_per_wave = cs_tpw(RPE / 32 <= 16 ? 16 : RPE / 32 <= 32 ? 32 : 64, true);
+  if (tiles_per_wave) *tiles_per_wave = cs_tpw(cs_xwm(R), true);
   return nrc * (d / 32);
 }
 
-static int embed_grad_cs_launch(const void *dpre, int32_t packed, int32_t V, int32_t d, int32_t R, int32_t ld_t,
-                                uint32_t *xt_bits, float *grad, float *bias_grad, uint32_t *tickets,
-                                const CsAdam *ad, void *stream, const CsReg *rg = nullptr, CsDw *dw = nullptr) {
-  int tpc, nrc;
-  size_t lds;
-  cs_plan(V, d, R, bias_grad != nullptr, tpc, nrc, lds, ad != nullptr, dw ? dw->nr : 0);
-  if (rg) lds += (size_t)((rg->nreg + 511) & ~511) * 4;
-  CC_REQUIRE(lds <= 160 * 1024 - 64, "cc_embed_grad_cs: R too large for the LDS stage");
-  if (dw) dw->nw1 = nrc * (d / 32);
-  const dim3 grid((unsigned)(nrc * (d / 32) + (dw ? dw->nr : 0)));
-  const int xw = ((R + 63) & ~63) / 32;  // bit words per row in the product
-  const bool vec = ((R + 31) / 32) % 4 == 0;  // xt rows 16-B aligned
-  const CsAdam a = ad ? *ad : CsAdam{};
-  const CsReg r = rg ? *rg : CsReg{};
-  hipStream_t s = as_stream(stream);
-#define CS_LAUNCH(PKV, XWMV, VECV, ADV)                                                                          \
-  do {                                                                                                           \
-    if constexpr (ADV) {                                                                                         \
-      if (dw) {                                                                                                  \
-        if (rg)                                                                                                  \
-          hipLaunchKernelGGL((embed_grad_cs_kernel<PKV, XWMV, VECV, true, true, true>), grid, dim3(CS_NT), lds, s, \
-                             (const bf16_t *)dpre, V, d, R, ld_t, tpc, xt_bits, grad, bias_grad, tickets, a, r, *dw); \
-        else                                                                                                     \
-          hipLaunchKernelGGL((embed_grad_cs_kernel<PKV, XWMV, VECV, true, false, true>), grid, dim3(CS_NT), lds, s, \
-                             (const bf16_t *)dpre, V, d, R, ld_t, tpc, xt_bits, grad, bias_grad, tickets, a, r, *dw); \
-        break;                                                                                                   \
-      }                                                                                                          \
-    }                                                                                                            \
-    if (rg)                                                                                                      \
-      hipLaunchKernelGGL((embed_grad_cs_kernel<PKV, XWMV, VECV, ADV, true>), grid, dim3(CS_NT), lds, s,          \
-                         (const bf16_t *)dpre, V, d, R, ld_t, tpc, xt_bits, grad, bias_grad, tickets, a, r, CsNoDw{}); \
-    else                                                                                                         \
-      hipLaunchKernelGGL((embed_grad_cs_kernel<PKV, XWMV, VECV, ADV>), grid, dim3(CS_NT), lds, s,                \
-                         (const bf16_t *)dpre, V, d, R, ld_t, tpc, xt_bits, grad, bias_grad, tickets, a, r, CsNoDw{}); \
-  } while (0)
-#define CS_LAUNCH2(XWMV, ADV)                                                                 \
-  if (packed) {                                                                               \
-    if (vec) CS_LAUNCH(true, XWMV, true, ADV); else CS_LAUNCH(true, XWMV, false, ADV);        \
-  } else {                                                                                    \
-    if (vec) CS_LAUNCH(false, XWMV, true, ADV); else CS_LAUNCH(false, XWMV, false, ADV);      \
-  }
-  if (ad) {
-    if (xw <= 16) { CS_LAUNCH2(16, true) } else if (xw <= 32) { CS_LAUNCH2(32, true) } else { CS_LAUNCH2(64, true) }
+// One call of the column-slice kernel, whichever of the six entries it came through: the operands
+// every form has, and what a form adds — TF Adam in the epilogue, the reg rows by index, the tower
+// dW jobs on rider workgroups (cc_tower_bwd_dw_direct's arguments; with Adam only).
+struct CsRiders {
+  const cc_tower_args *tower;
+  int32_t n;
+};
+struct CsCall {
+  const void *dpre;
+  int32_t packed, V, d, R, ld_t;
+  uint32_t *xt_bits;
+  float *grad, *bias_grad;  // grad: the forms without Adam (with it the W1 gradient is never stored)
+  uint32_t *tickets;
+  void *stream;
+  const CsAdam *ad = nullptr;
+  const CsReg *rg = nullptr;
+  const CsRiders *rd = nullptr;
+};
+
+// every argument check of the six entries, in the order a caller sees them; fills dw (rider forms)
+static int cs_check(const char *who, const CsCall &c, CsDw &dw) {
+  const std::string w = std::string(who) + ": ";
+  if (const CsAdam *ad = c.ad) {
+    CC_REQUIRE(c.dpre && c.xt_bits && ad->p && ad->m && ad->v && ad->shadow && ad->state, w + "null pointer");
+    CC_REQUIRE((((uintptr_t)ad->p | (uintptr_t)ad->m | (uintptr_t)ad->v | (uintptr_t)c.bias_grad) & 15) == 0 &&
+                   ((uintptr_t)ad->shadow & 7) == 0,
+               w + "p, m, v, bias_grad 16-B aligned, shadow 8-B aligned");
   } else {
-    if (xw <= 16) { CS_LAUNCH2(16, false) } else if (xw <= 32) { CS_LAUNCH2(32, false) } else { CS_LAUNCH2(64, false) }
+    CC_REQUIRE(c.dpre && c.xt_bits && c.grad, w + "null pointer");
+    CC_REQUIRE((((uintptr_t)c.grad | (uintptr_t)c.bias_grad) & 15) == 0, w + "grad / bias_grad 16-B aligned");
   }
-#undef CS_LAUNCH2
-#undef CS_LAUNCH
+  CC_REQUIRE(c.d % 32 == 0 && c.d >= 32 && c.d <= 4096, w + "d must be a multiple of 32");
+  // (card0, a row chunk's first card: an argument of the reg form without Adam — with it, all of W1 and 0)
+  CC_REQUIRE(c.V > 0 && c.R > 0 && c.R <= 2048 && (!c.rg || c.rg->card0 >= 0),
+             w + (c.rg && !c.ad ? "V > 0, R in 1..2048, card0 >= 0" : "V > 0, R in 1..2048"));
+  CC_REQUIRE(c.ld_t % 64 == 0 && c.ld_t >= c.R && ((uintptr_t)c.dpre % 16) == 0,
+             w + "ld_t must be a multiple of 64 covering R, dPre1 image 16-B aligned");
+  if (const CsReg *rg = c.rg) {
+    CC_REQUIRE(rg->rid && rg->nreg >= 1 && rg->nreg <= CS_REG_MAX, w + "reg_idx non-null, nreg in 1..512");
+    CC_REQUIRE(rg->k0 >= 0 && 16 * rg->k0 >= c.R && 16 * (rg->k0 + (rg->nreg + 15) / 16) <= c.ld_t,
+               w + "reg rows past the product's rows and inside the dPre1 image (16 reg_k0 >= R, 16 (reg_k0 + "
+                   "ceil(nreg / 16)) <= ld_t)");
+  }
+  if (c.rd) {  // cc_tower_bwd_dw_direct's checks (tower.hip) and the rider count
+    CC_REQUIRE(c.rd->n >= 1 && c.rd->n <= 64, w + "n_riders in 1..64");
+    if (int rc = cctower::dw_rider_params(c.rd->tower, dw.tp, dw.jobs, who)) return rc;
+    dw.nr = c.rd->n;  // (nw1: set with the launch geometry)
+  }
+  return CC_OK;
+}
+
+// f(std::bool_constant<b>...) for the runtime flags b...: each becomes a compile-time constant
+template <class F> static void with_flags(F &&f) { f(); }
+template <class F, class... Bs> static void with_flags(F &&f, bool b, Bs... bs) {
+  if (b) with_flags([&](auto... cs) { f(std::true_type{}, cs...); }, bs...);
+  else with_flags([&](auto... cs) { f(std::false_type{}, cs...); }, bs...);
+}
+
+// the six entries' body: the checks, the launch geometry, the instance
+static int cs_run(const char *who, const CsCall &c) {
+  CsDw dwa, *dw = c.rd ? &dwa : nullptr;  // the riders' kernel arguments (rider forms)
+  if (int rc = cs_check(who, c, dwa)) return rc;
+  const int xwm = cs_xwm(c.R);
+  const bool adam = c.ad != nullptr;
+  const size_t lds = (size_t)cs_lds(xwm, adam, c.rg ? c.rg->nreg : 0).total;
+  CC_REQUIRE(lds <= (size_t)CS_LDS_MAX, "cc_embed_grad_cs: R too large for the LDS stage");
+  int tpc, nrc;
+  cs_plan(c.V, c.d, c.R, c.bias_grad != nullptr, tpc, nrc, adam, dw ? dw->nr : 0);
+  if (dw) dw->nw1 = nrc * (c.d / 32);
+  const dim3 grid((unsigned)(nrc * (c.d / 32) + (dw ? dw->nr : 0)));
+  const bool vec = ((c.R + 31) / 32) % 4 == 0;  // xt rows 16-B aligned
+  const CsAdam a = c.ad ? *c.ad : CsAdam{};
+  const CsReg r = c.rg ? *c.rg : CsReg{};
+  // one instance per (XWM, packed, vec, adam, reg, riders) that can launch: none with Adam at
+  // XWM = 64 (the LDS check above has turned those shapes away, see cs_lds), riders only with Adam
+  auto launch = [&](auto xw, auto pk, auto vc, auto am, auto rg, auto rd) {
+    constexpr int XWM = decltype(xw)::value;
+    constexpr bool PK = decltype(pk)::value, VEC = decltype(vc)::value, ADAM = decltype(am)::value,
+                   REG = decltype(rg)::value, DW = decltype(rd)::value;
+    if constexpr (!(ADAM && XWM == 64) && !(DW && !ADAM)) {
+      std::conditional_t<DW, CsDw, CsNoDw> riders{};
+      if constexpr (DW) riders = *dw;
+      hipLaunchKernelGGL((embed_grad_cs_kernel<PK, XWM, VEC, ADAM, REG, DW>), grid, dim3(CS_NT), lds,
+                         as_stream(c.stream), (const bf16_t *)c.dpre, c.V, c.d, c.R, c.ld_t, tpc, c.xt_bits, c.grad,
+                         c.bias_grad, c.tickets, a, r, riders);
+    }
+  };
+  auto select = [&](auto xw) {
+    with_flags([&](auto... flags) { launch(xw, flags...); }, c.packed != 0, vec, adam, c.rg != nullptr, dw != nullptr);
+  };
+  if (xwm == 16) select(std::integral_constant<int, 16>{});
+  else if (xwm == 32) select(std::integral_constant<int, 32>{});
+  else select(std::integral_constant<int, 64>{});
   CC_LAUNCH_CHECK("embed_grad_cs_kernel");
   return CC_OK;
 }
 
 extern "C" int cc_embed_grad_cs(const void *dpre, int32_t packed, int32_t V, int32_t d, int32_t R, int32_t ld_t,
                                 uint32_t *xt_bits, float *grad, float *bias_grad, uint32_t *tickets, void *stream) {
-  CC_REQUIRE(dpre && xt_bits && grad, "cc_embed_grad_cs: null pointer");
-  CC_REQUIRE((((uintptr_t)grad | (uintptr_t)bias_grad) & 15) == 0, "cc_embed_grad_cs: grad / bias_grad 16-B aligned");
-  CC_REQUIRE(d % 32 == 0 && d >= 32 && d <= 4096, "cc_embed_grad_cs: d must be a multiple of 32");
-  CC_REQUIRE(V > 0 && R > 0 && R <= 2048, "cc_embed_grad_cs: V > 0, R in 1..2048");
-  CC_REQUIRE(ld_t % 64 == 0 && ld_t >= R && ((uintptr_t)dpre % 16) == 0,
-             "cc_embed_grad_cs: ld_t must be a multiple of 64 covering R, dPre1 image 16-B aligned");
-  return embed_grad_cs_launch(dpre, packed, V, d, R, ld_t, xt_bits, grad, bias_grad, tickets, nullptr, stream);
+  return cs_run("cc_embed_grad_cs", {dpre, packed, V, d, R, ld_t, xt_bits, grad, bias_grad, tickets, stream});
 }
 
 extern "C" int cc_embed_grad_cs_adam(const void *dpre, int32_t packed, int32_t V, int32_t d, int32_t R,
                                      int32_t ld_t, uint32_t *xt_bits, float *bias_grad, uint32_t *tickets, float *p,
                                      float *m, float *v, uint16_t *shadow, const int64_t *state, float lr,
                                      float beta1, float beta2, float eps, void *stream) {
-  CC_REQUIRE(dpre && xt_bits && p && m && v && shadow && state, "cc_embed_grad_cs_adam: null pointer");
-  CC_REQUIRE((((uintptr_t)p | (uintptr_t)m | (uintptr_t)v | (uintptr_t)bias_grad) & 15) == 0 &&
-                 ((uintptr_t)shadow & 7) == 0,
-             "cc_embed_grad_cs_adam: p, m, v, bias_grad 16-B aligned, shadow 8-B aligned");
-  CC_REQUIRE(d % 32 == 0 && d >= 32 && d <= 4096, "cc_embed_grad_cs_adam: d must be a multiple of 32");
-  CC_REQUIRE(V > 0 && R > 0 && R <= 2048, "cc_embed_grad_cs_adam: V > 0, R in 1..2048");
-  CC_REQUIRE(ld_t % 64 == 0 && ld_t >= R && ((uintptr_t)dpre % 16) == 0,
-             "cc_embed_grad_cs_adam: ld_t must be a multiple of 64 covering R, dPre1 image 16-B aligned");
   const CsAdam ad{p, m, v, (bf16_t *)shadow, state, lr, beta1, beta2, eps};
-  return embed_grad_cs_launch(dpre, packed, V, d, R, ld_t, xt_bits, nullptr, bias_grad, tickets, &ad, stream);
-}
-
-static const char *cs_reg_check(const int32_t *reg_idx, int32_t nreg, int32_t reg_k0, int32_t R, int32_t ld_t) {
-  if (!reg_idx || nreg < 1 || nreg > CS_REG_MAX) return "reg_idx non-null, nreg in 1..512";
-  if (reg_k0 < 0 || 16 * reg_k0 < R || 16 * (reg_k0 + (nreg + 15) / 16) > ld_t)
-    return "reg rows past the product's rows and inside the dPre1 image (16 reg_k0 >= R, 16 (reg_k0 + ceil(nreg / 16)) <= ld_t)";
-  return nullptr;
+  return cs_run("cc_embed_grad_cs_adam",
+                {dpre, packed, V, d, R, ld_t, xt_bits, nullptr, bias_grad, tickets, stream, &ad});
 }
 
 extern "C" int cc_embed_grad_cs_reg(const void *dpre, int32_t packed, int32_t V, int32_t d, int32_t R, int32_t ld_t,
                                     uint32_t *xt_bits, float *grad, float *bias_grad, uint32_t *tickets,
                                     const int32_t *reg_idx, int32_t nreg, int32_t reg_k0, int32_t card0, void *stream) {
-  CC_REQUIRE(dpre && xt_bits && grad, "cc_embed_grad_cs_reg: null pointer");
-  CC_REQUIRE((((uintptr_t)grad | (uintptr_t)bias_grad) & 15) == 0, "cc_embed_grad_cs_reg: grad / bias_grad 16-B aligned");
-  CC_REQUIRE(d % 32 == 0 && d >= 32 && d <= 4096, "cc_embed_grad_cs_reg: d must be a multiple of 32");
-  CC_REQUIRE(V > 0 && R > 0 && R <= 2048 && card0 >= 0, "cc_embed_grad_cs_reg: V > 0, R in 1..2048, card0 >= 0");
-  CC_REQUIRE(ld_t % 64 == 0 && ld_t >= R && ((uintptr_t)dpre % 16) == 0,
-             "cc_embed_grad_cs_reg: ld_t must be a multiple of 64 covering R, dPre1 image 16-B aligned");
-  const char *e = cs_reg_check(reg_idx, nreg, reg_k0, R, ld_t);
-  CC_REQUIRE(!e, e);
   const CsReg rg{reg_idx, nreg, reg_k0, card0};
-  return embed_grad_cs_launch(dpre, packed, V, d, R, ld_t, xt_bits, grad, bias_grad, tickets, nullptr, stream, &rg);
+  return cs_run("cc_embed_grad_cs_reg",
+                {dpre, packed, V, d, R, ld_t, xt_bits, grad, bias_grad, tickets, stream, nullptr, &rg});
 }
 
 extern "C" int cc_embed_grad_cs_adam_reg(const void *dpre, int32_t packed, int32_t V, int32_t d, int32_t R,
@@ -1347,29 +1379,10 @@ extern "C" int cc_embed_grad_cs_adam_reg(const void *dpre, int32_t packed, int32
                                          float *m, float *v, uint16_t *shadow, const int64_t *state, float lr,
                                          float beta1, float beta2, float eps, const int32_t *reg_idx, int32_t nreg,
                                          int32_t reg_k0, void *stream) {
-  CC_REQUIRE(dpre && xt_bits && p && m && v && shadow && state, "cc_embed_grad_cs_adam_reg: null pointer");
-  CC_REQUIRE((((uintptr_t)p | (uintptr_t)m | (uintptr_t)v | (uintptr_t)bias_grad) & 15) == 0 &&
-                 ((uintptr_t)shadow & 7) == 0,
-             "cc_embed_grad_cs_adam_reg: p, m, v, bias_grad 16-B aligned, shadow 8-B aligned");
-  CC_REQUIRE(d % 32 == 0 && d >= 32 && d <= 4096, "cc_embed_grad_cs_adam_reg: d must be a multiple of 32");
-  CC_REQUIRE(V > 0 && R > 0 && R <= 2048, "cc_embed_grad_cs_adam_reg: V > 0, R in 1..2048");
-  CC_REQUIRE(ld_t % 64 == 0 && ld_t >= R && ((uintptr_t)dpre % 16) == 0,
-             "cc_embed_grad_cs_adam_reg: ld_t must be a multiple of 64 covering R, dPre1 image 16-B aligned");
-  const char *e = cs_reg_check(reg_idx, nreg, reg_k0, R, ld_t);
-  CC_REQUIRE(!e, e);
   const CsAdam ad{p, m, v, (bf16_t *)shadow, state, lr, beta1, beta2, eps};
   const CsReg rg{reg_idx, nreg, reg_k0, 0};
-  return embed_grad_cs_launch(dpre, packed, V, d, R, ld_t, xt_bits, nullptr, bias_grad, tickets, &ad, stream, &rg);
-}
-
-// the rider forms: cc_tower_bwd_dw_direct's checks (tower.hip), the rider count, then the same launch
-static int cs_dw_args(const cc_tower_args *tower, int32_t n_riders, CsDw &dw, const char *who) {
-  CC_REQUIRE(n_riders >= 1 && n_riders <= 64, std::string(who) + ": n_riders in 1..64");
-  int rc = cctower::dw_rider_params(tower, dw.tp, dw.jobs, who);
-  if (rc) return rc;
-  dw.nr = n_riders;
-  dw.nw1 = 0;  // (set with the launch geometry)
-  return CC_OK;
+  return cs_run("cc_embed_grad_cs_adam_reg",
+                {dpre, packed, V, d, R, ld_t, xt_bits, nullptr, bias_grad, tickets, stream, &ad, &rg});
 }
 
 extern "C" int cc_embed_grad_cs_adam_dw(const void *dpre, int32_t packed, int32_t V, int32_t d, int32_t R,
@@ -1377,20 +1390,10 @@ extern "C" int cc_embed_grad_cs_adam_dw(const void *dpre, int32_t packed, int32_
                                         float *p, float *m, float *v, uint16_t *shadow, const int64_t *state,
                                         float lr, float beta1, float beta2, float eps, const cc_tower_args *tower,
                                         int32_t n_riders, void *stream) {
-  CC_REQUIRE(dpre && xt_bits && p && m && v && shadow && state, "cc_embed_grad_cs_adam_dw: null pointer");
-  CC_REQUIRE((((uintptr_t)p | (uintptr_t)m | (uintptr_t)v | (uintptr_t)bias_grad) & 15) == 0 &&
-                 ((uintptr_t)shadow & 7) == 0,
-             "cc_embed_grad_cs_adam_dw: p, m, v, bias_grad 16-B aligned, shadow 8-B aligned");
-  CC_REQUIRE(d % 32 == 0 && d >= 32 && d <= 4096, "cc_embed_grad_cs_adam_dw: d must be a multiple of 32");
-  CC_REQUIRE(V > 0 && R > 0 && R <= 2048, "cc_embed_grad_cs_adam_dw: V > 0, R in 1..2048");
-  CC_REQUIRE(ld_t % 64 == 0 && ld_t >= R && ((uintptr_t)dpre % 16) == 0,
-             "cc_embed_grad_cs_adam_dw: ld_t must be a multiple of 64 covering R, dPre1 image 16-B aligned");
-  CsDw dw;
-  int rc = cs_dw_args(tower, n_riders, dw, "cc_embed_grad_cs_adam_dw");
-  if (rc) return rc;
   const CsAdam ad{p, m, v, (bf16_t *)shadow, state, lr, beta1, beta2, eps};
-  return embed_grad_cs_launch(dpre, packed, V, d, R, ld_t, xt_bits, nullptr, bias_grad, tickets, &ad, stream, nullptr,
-                              &dw);
+  const CsRiders rd{tower, n_riders};
+  return cs_run("cc_embed_grad_cs_adam_dw",
+                {dpre, packed, V, d, R, ld_t, xt_bits, nullptr, bias_grad, tickets, stream, &ad, nullptr, &rd});
 }
 
 extern "C" int cc_embed_grad_cs_adam_reg_dw(const void *dpre, int32_t packed, int32_t V, int32_t d, int32_t R,
@@ -1399,23 +1402,11 @@ extern "C" int cc_embed_grad_cs_adam_reg_dw(const void *dpre, int32_t packed, in
                                             float lr, float beta1, float beta2, float eps, const int32_t *reg_idx,
                                             int32_t nreg, int32_t reg_k0, const cc_tower_args *tower,
                                             int32_t n_riders, void *stream) {
-  CC_REQUIRE(dpre && xt_bits && p && m && v && shadow && state, "cc_embed_grad_cs_adam_reg_dw: null pointer");
-  CC_REQUIRE((((uintptr_t)p | (uintptr_t)m | (uintptr_t)v | (uintptr_t)bias_grad) & 15) == 0 &&
-                 ((uintptr_t)shadow & 7) == 0,
-             "cc_embed_grad_cs_adam_reg_dw: p, m, v, bias_grad 16-B aligned, shadow 8-B aligned");
-  CC_REQUIRE(d % 32 == 0 && d >= 32 && d <= 4096, "cc_embed_grad_cs_adam_reg_dw: d must be a multiple of 32");
-  CC_REQUIRE(V > 0 && R > 0 && R <= 2048, "cc_embed_grad_cs_adam_reg_dw: V > 0, R in 1..2048");
-  CC_REQUIRE(ld_t % 64 == 0 && ld_t >= R && ((uintptr_t)dpre % 16) == 0,
-             "cc_embed_grad_cs_adam_reg_dw: ld_t must be a multiple of 64 covering R, dPre1 image 16-B aligned");
-  const char *e = cs_reg_check(reg_idx, nreg, reg_k0, R, ld_t);
-  CC_REQUIRE(!e, e);
-  CsDw dw;
-  int rc = cs_dw_args(tower, n_riders, dw, "cc_embed_grad_cs_adam_reg_dw");
-  if (rc) return rc;
   const CsAdam ad{p, m, v, (bf16_t *)shadow, state, lr, beta1, beta2, eps};
   const CsReg rg{reg_idx, nreg, reg_k0, 0};
-  return embed_grad_cs_launch(dpre, packed, V, d, R, ld_t, xt_bits, nullptr, bias_grad, tickets, &ad, stream, &rg,
-                              &dw);
+  const CsRiders rd{tower, n_riders};
+  return cs_run("cc_embed_grad_cs_adam_reg_dw",
+                {dpre, packed, V, d, R, ld_t, xt_bits, nullptr, bias_grad, tickets, stream, &ad, &rg, &rd});
 }
 
 extern "C" int cc_embed_gather_fwd_warm(int32_t dtype, const void *table, const float *bias, int32_t V,

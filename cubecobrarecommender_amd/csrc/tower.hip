@@ -1401,23 +1401,34 @@ extern "C" int cc_tower_bwd(const cc_tower_args *t, void *stream) {
 extern "C" int cc_tower_bwd_chain(const cc_tower_args *t, void *stream) {
   return tower_bwd_launch(t, stream, true, false);
 }
+// TF Adam over [lo0, lo0 + n0) and [lo1, lo1 + n1) of the flat buffers beside the chains: entry
+// `who`'s checks of the buffers and the ranges, then the two ranges' arguments
+static int chain_adam_args(const char *who, const char *null_what, float *p, float *m, float *v, const float *g,
+                           uint16_t *shadow, int64_t lo0, int64_t n0, int64_t lo1, int64_t n1, const int64_t *state,
+                           float lr, float beta1, float beta2, float eps, cc_adam::Args (&a)[2]) {
+  const std::string w = std::string(who) + ": ";
+  CC_REQUIRE(p && m && v && g && state, w + null_what);
+  CC_REQUIRE(((uintptr_t)p | (uintptr_t)m | (uintptr_t)v | (uintptr_t)g) % 16 == 0 && lo0 % 4 == 0 && lo1 % 4 == 0,
+             w + "buffers must be 16-byte aligned, range starts multiples of 4");
+  CC_REQUIRE(!shadow || (uintptr_t)shadow % 8 == 0, w + "shadow must be 8-byte aligned");
+  CC_REQUIRE(lo0 >= 0 && n0 >= 0 && n1 >= 0 && (n1 == 0 || lo1 >= lo0 + n0), w + "ranges");
+  bf16_t *sh = (bf16_t *)shadow;
+  a[0] = {p + lo0, m + lo0, v + lo0, g + lo0, sh ? sh + lo0 : nullptr, n0, lr, beta1, beta2, eps, lo0};
+  a[1] = {p + lo1, m + lo1, v + lo1, g + lo1, sh ? sh + lo1 : nullptr, n1, lr, beta1, beta2, eps, lo1};
+  return CC_OK;
+}
 extern "C" int cc_tower_bwd_chain_adam(const cc_tower_args *t, float *p, float *m, float *v, const float *g,
                                        uint16_t *shadow, int64_t lo0, int64_t n0, int64_t lo1, int64_t n1,
                                        const int64_t *state, float lr, float beta1, float beta2, float eps,
                                        void *stream) {
   CC_REQUIRE(t && t->dtype == CC_BF16 && t->d <= 256,
              "cc_tower_bwd_chain_adam: the bf16 fast chains (d <= 256) only");
-  CC_REQUIRE(p && m && v && g && state, "cc_tower_bwd_chain_adam: null pointer");
-  CC_REQUIRE(((uintptr_t)p | (uintptr_t)m | (uintptr_t)v | (uintptr_t)g) % 16 == 0 && lo0 % 4 == 0 && lo1 % 4 == 0,
-             "cc_tower_bwd_chain_adam: buffers must be 16-byte aligned, range starts multiples of 4");
-  CC_REQUIRE(!shadow || (uintptr_t)shadow % 8 == 0, "cc_tower_bwd_chain_adam: shadow must be 8-byte aligned");
-  CC_REQUIRE(lo0 >= 0 && n0 >= 0 && n1 >= 0 && (n1 == 0 || lo1 >= lo0 + n0), "cc_tower_bwd_chain_adam: ranges");
+  cc_adam::Args a[2];
+  if (int rc = chain_adam_args("cc_tower_bwd_chain_adam", "null pointer", p, m, v, g, shadow, lo0, n0, lo1, n1, state,
+                               lr, beta1, beta2, eps, a))
+    return rc;
   const int64_t n = n0 + n1;
   if (n == 0) return tower_bwd_launch(t, stream, true, false);
-  const cc_adam::Args a{p + lo0, m + lo0, v + lo0, g + lo0, shadow ? (bf16_t *)shadow + lo0 : nullptr, n0,
-                        lr, beta1, beta2, eps, lo0};
-  const cc_adam::Args a1{p + lo1, m + lo1, v + lo1, g + lo1, shadow ? (bf16_t *)shadow + lo1 : nullptr, n1,
-                         lr, beta1, beta2, eps, lo1};
   // one 512-thread block per CU beside the chains (their VGPR budget admits one per CU), capped
   // so no block runs out of work
   static int cus = 0;
@@ -1429,7 +1440,7 @@ extern "C" int cc_tower_bwd_chain_adam(const cc_tower_args *t, float *p, float *
   }
   const int64_t want = cdiv(cdiv(n, 4), (int64_t)FNT * 4);
   const int blocks = (int)std::max<int64_t>(1, std::min<int64_t>(want, std::max(cus - t->R / RB, 8)));
-  return tower_bwd_launch(t, stream, true, false, &a, state, blocks, &a1);
+  return tower_bwd_launch(t, stream, true, false, &a[0], state, blocks, &a[1]);
 }
 // the chains + F of the NEXT step (cc_noise_fwd's arguments; {step, batch, epoch} advanced as the
 // Adam + F launch does) + optionally TF Adam over [lo0, lo0 + n0) and [lo1, lo1 + n1) (n0 = n1 = 0:
@@ -1453,18 +1464,13 @@ extern "C" int cc_tower_bwd_chain_noise(const cc_tower_args *t, const cc_noise_a
   const int64_t n = n0 + n1;
   if (n == 0)
     return tower_bwd_launch(t, stream, true, false, nullptr, nullptr, 0, nullptr, next, batches_per_epoch);
-  CC_REQUIRE(p && m && v && g && state, "cc_tower_bwd_chain_noise: null Adam pointer");
-  CC_REQUIRE(((uintptr_t)p | (uintptr_t)m | (uintptr_t)v | (uintptr_t)g) % 16 == 0 && lo0 % 4 == 0 && lo1 % 4 == 0,
-             "cc_tower_bwd_chain_noise: buffers must be 16-byte aligned, range starts multiples of 4");
-  CC_REQUIRE(!shadow || (uintptr_t)shadow % 8 == 0, "cc_tower_bwd_chain_noise: shadow must be 8-byte aligned");
-  CC_REQUIRE(lo0 >= 0 && n0 >= 0 && n1 >= 0 && (n1 == 0 || lo1 >= lo0 + n0), "cc_tower_bwd_chain_noise: ranges");
-  const cc_adam::Args a{p + lo0, m + lo0, v + lo0, g + lo0, shadow ? (bf16_t *)shadow + lo0 : nullptr, n0,
-                        lr, beta1, beta2, eps, lo0};
-  const cc_adam::Args a1{p + lo1, m + lo1, v + lo1, g + lo1, shadow ? (bf16_t *)shadow + lo1 : nullptr, n1,
-                         lr, beta1, beta2, eps, lo1};
+  cc_adam::Args a[2];
+  if (int rc = chain_adam_args("cc_tower_bwd_chain_noise", "null Adam pointer", p, m, v, g, shadow, lo0, n0, lo1, n1,
+                               state, lr, beta1, beta2, eps, a))
+    return rc;
   const int64_t want = cdiv(cdiv(n, 4), (int64_t)FNT * 4);
   const int blocks = (int)std::max<int64_t>(1, std::min<int64_t>(want, 256));
-  return tower_bwd_launch(t, stream, true, false, &a, state, blocks, &a1, next, batches_per_epoch);
+  return tower_bwd_launch(t, stream, true, false, &a[0], state, blocks, &a[1], next, batches_per_epoch);
 }
 
 extern "C" int cc_tower_bwd_dw(const cc_tower_args *t, void *stream) {

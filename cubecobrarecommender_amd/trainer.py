@@ -989,36 +989,28 @@ class Trainer:
         t = self._tick('cc_embed_scatter_bwd')
         XR = self.xt_rows          # rows in the bitmask product (full mode: the cubes only)
         chunks = self.layout.w1_chunks if self.layout.group_biases else [(0, V)]
+        # the column-slice forms (_lib.w1_grad_name): + the reg rows by index (rows B .. of the dPre1
+        # image), + the tower dW jobs on rider workgroups — a form's arguments follow in that order
+        reg = (L.ptr(self.reg_idx), self.Breg, cfg.batch_size // 16) if self.reg_by_index else ()
         if self.fuse_w1:   # column slices + TF Adam on W1 in the epilogue
             cfg_ = self.cfg
             src, pk = (self.gpre1p, 1) if self.gpre1p is not None else (self.gPre1T, 0)
             w1 = (L.ptr(src), pk, V, d, XR, self.RP, L.ptr(self.xt_bits), self.gp('encoder/encoded_1/bias'),
                   self._eg_tk(), L.ptr(self.params), L.ptr(self.m), L.ptr(self.v), L.ptr(self.shadow),
                   L.ptr(self.state), cfg_.lr, cfg_.beta1, cfg_.beta2, cfg_.eps)
-            if self.dw_in_w1 and self.reg_by_index:   # + the tower dW jobs on rider workgroups
-                L.call('cc_embed_grad_cs_adam_reg_dw', *w1, L.ptr(self.reg_idx), self.Breg, cfg.batch_size // 16,
-                       L.C.byref(self.targs), self.dw_in_w1, s)
-            elif self.dw_in_w1:
-                L.call('cc_embed_grad_cs_adam_dw', *w1, L.C.byref(self.targs), self.dw_in_w1, s)
-            elif self.reg_by_index:   # + the reg rows by index (rows B .. of the dPre1 image)
-                L.call('cc_embed_grad_cs_adam_reg', *w1, L.ptr(self.reg_idx), self.Breg, cfg.batch_size // 16, s)
-            else:
-                L.call('cc_embed_grad_cs_adam', *w1, s)
+            riders = (L.C.byref(self.targs), self.dw_in_w1) if self.dw_in_w1 else ()
+            L.call(L.w1_grad_name(True, bool(reg), bool(riders)), *w1, *reg, *riders, s)
         elif self.eg_tickets is not None:   # column slices (cc_embed_grad_cs), from the packed image or dPre1^T
             src, pk = (self.gpre1p, 1) if self.gpre1p is not None else (self.gPre1T, 0)
             # data parallel: W1's row chunks one launch each (the bias row with the last), each
             # chunk's exchange starting as soon as its launch is issued (zero.py bucket hooks);
             # every W1 tile is computed as in the one-launch product (bit-identical)
             gw, gb = self.layout.offset('encoder/encoded_1/kernel'), self.gp('encoder/encoded_1/bias')
+            name = L.w1_grad_name(False, bool(reg))
             for i, (r0, r1) in enumerate(chunks):
                 gbi = gb if i == len(chunks) - 1 else None
-                if self.reg_by_index:
-                    L.call('cc_embed_grad_cs_reg', L.ptr(src), pk, r1 - r0, d, XR, self.RP, L.ptr(self.xt_bits[r0:]),
-                           L.ptr(self.grads[gw + r0 * d:]), gbi, self._eg_tk(), L.ptr(self.reg_idx), self.Breg,
-                           cfg.batch_size // 16, r0, s)
-                else:
-                    L.call('cc_embed_grad_cs', L.ptr(src), pk, r1 - r0, d, XR, self.RP, L.ptr(self.xt_bits[r0:]),
-                           L.ptr(self.grads[gw + r0 * d:]), gbi, self._eg_tk(), s)
+                L.call(name, L.ptr(src), pk, r1 - r0, d, XR, self.RP, L.ptr(self.xt_bits[r0:]),
+                       L.ptr(self.grads[gw + r0 * d:]), gbi, self._eg_tk(), *reg, *((r0,) if reg else ()), s)
                 if i + 1 < len(chunks):
                     self._fire_bucket(f'w1_{i}')
         else:

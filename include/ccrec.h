@@ -224,7 +224,9 @@ int32_t cc_embed_grad_cs_tickets(int32_t V, int32_t d, int32_t R);
  * kernel's epilogue (one process: the gradient is final there): p, m, v are W1's rows [V][d] of
  * the flat fp32 buffers, shadow its bf16 rows; the W1 gradient itself is never stored, the bias
  * gradient goes to bias_grad for the main Adam launch (which then starts after W1).  Bit-identical
- * parameters / moments to cc_embed_grad_cs followed by cc_adam_dense over W1. */
+ * parameters / moments to cc_embed_grad_cs followed by cc_adam_dense over W1.  R <= 1024 for this
+ * and every other _adam form below (the epilogue's tiles share the LDS with the dPre1 slice; a
+ * taller product is CC_ERR_ARG, "R too large for the LDS stage"). */
 int cc_embed_grad_cs_adam(const void *dpre, int32_t packed, int32_t V, int32_t d, int32_t R, int32_t ld_t,
                           uint32_t *xt_bits, float *bias_grad, uint32_t *tickets, float *p, float *m, float *v,
                           uint16_t *shadow, const int64_t *state, float lr, float beta1, float beta2, float eps,

@@ -28,6 +28,23 @@ def test_library_exports_every_declared_symbol():
     assert lib.cc_abi_version() == 2
 
 
+def test_w1_gradient_signatures_are_the_hand_written_lists():
+    """_lib builds the six cc_embed_grad_cs* signatures from shared pieces; the result is these
+    lists, written out argument by argument from include/ccrec.h."""
+    P, I, F, T = ctypes.c_void_p, ctypes.c_int32, ctypes.c_float, ctypes.POINTER(L.TowerArgs)
+    want = {
+        'cc_embed_grad_cs': [P, I, I, I, I, I, P, P, P, P, P],
+        'cc_embed_grad_cs_adam': [P, I, I, I, I, I, P, P, P, P, P, P, P, P, F, F, F, F, P],
+        'cc_embed_grad_cs_reg': [P, I, I, I, I, I, P, P, P, P, P, I, I, I, P],
+        'cc_embed_grad_cs_adam_reg': [P, I, I, I, I, I, P, P, P, P, P, P, P, P, F, F, F, F, P, I, I, P],
+        'cc_embed_grad_cs_adam_dw': [P, I, I, I, I, I, P, P, P, P, P, P, P, P, F, F, F, F, T, I, P],
+        'cc_embed_grad_cs_adam_reg_dw': [P, I, I, I, I, I, P, P, P, P, P, P, P, P, F, F, F, F, P, I, I, T, I, P],
+    }
+    assert sorted(L.w1_grad_name(*f) for f in L.W1_GRAD_FORMS) == sorted(want)
+    for name, args in want.items():
+        assert L.SIGNATURES[name] == (ctypes.c_int, args), name
+
+
 def test_param_layout_matches_python_mirror():
     lib = L.lib()
     for V, d in ((20884, 512), (22000, 256), (700, 64), (22000, 1024)):

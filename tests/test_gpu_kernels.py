@@ -576,7 +576,8 @@ def test_embed_grad_packed_bit_exact(V, R):
 
 
 @pytest.mark.parametrize('V,R,d', [(22000, 512, 256), (3000, 512, 256), (777, 96, 256), (22000, 1024, 256),
-                                   (5000, 1024, 1024), (1500, 200, 128), (64, 32, 32)])
+                                   (5000, 1024, 1024), (1500, 200, 128), (64, 32, 32),
+                                   (777, 1056, 128), (777, 2048, 128)])   # 1024 < R: scalar / 16-B bit loads
 def test_embed_grad_cs_bit_exact(V, R, d):
     """cc_embed_grad_cs (column slices: the dPre1 slice and the chunk's bit words staged in LDS
     once, A fragments from a nibble LUT) equals cc_embed_grad_mfma bit for bit (same MFMA k order),

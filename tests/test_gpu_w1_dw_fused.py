@@ -97,8 +97,10 @@ def _compare(V, d, R, Bt, Rt, nreg, packed, rider_counts, seed):
 
 # V = 2504: 27 chunks x 8 slices = 216 W1 workgroups, room for the riders as it is; V = 8184, R = 512:
 # 256 tiles, one per CU — the reserve mode re-chunks; d = 128: the unpacked dPre1^T source, 4 slices;
-# V = 2500: a partial last tile (the bias row inside it) and a short last chunk
-@pytest.mark.parametrize('V,d,R', [(2504, 256, 128), (8184, 256, 512), (8184, 128, 256), (2500, 256, 128)])
+# V = 2500: a partial last tile (the bias row inside it) and a short last chunk; R = 1024: the
+# rider form of the 32-word instance (1024 tower rows: still one wave per dW tile)
+@pytest.mark.parametrize('V,d,R', [(2504, 256, 128), (8184, 256, 512), (8184, 128, 256), (2500, 256, 128),
+                                   (2504, 256, 1024)])
 def test_fused_launch_matches_the_two_launches(V, d, R):
     """All six tower gw / gb, W1's p / m / v / shadow and the W1 bias gradient, with 1 rider (it
     walks all 208 jobs at d = 256) and the default 16."""
