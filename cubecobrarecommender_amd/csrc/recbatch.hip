@@ -28,6 +28,9 @@
 //   rank_rows_kernel: one workgroup per row sorts all V (key', card) pairs (stable LSD radix
 //                     sort, three 10-bit passes through two ping-pong buffers in the workspace)
 //                     and writes the first want entries of the descending order.
+// cc_recommend_batch_target_ranks_fp32 runs the same chain and then, instead of ranking the row,
+//   target_ranks_kernel: one workgroup per row counts, for each of the row's chosen target cards,
+//                     the candidates ranked before it (held-out evaluation; see the kernel).
 #include "common.hpp"
 #include "detmath.hpp"
 #include "topn_tiles.hpp"
@@ -205,6 +208,27 @@ __device__ __forceinline__ int block_incl_scan(int v, int *wtot) {
   return before + x;
 }
 
+// Bitonic sort of a[0 .. P) in LDS, descending, by the whole SNT-thread block; P a power of two,
+// the entries written and a barrier passed before the call.  Every step ends with a barrier.
+__device__ __forceinline__ void bitonic_sort_desc(uint64_t *a, int P) {
+  const int tid = threadIdx.x;
+  for (int size = 2; size <= P; size <<= 1)
+    for (int stride = size >> 1; stride > 0; stride >>= 1) {
+      for (int i = tid; i < P; i += SNT) {
+        const int pr = i ^ stride;
+        if (pr > i) {
+          const bool down = (i & size) == 0;
+          const uint64_t x = a[i], y = a[pr];
+          if ((x < y) == down) {
+            a[i] = y;
+            a[pr] = x;
+          }
+        }
+      }
+      __syncthreads();
+    }
+}
+
 __global__ __launch_bounds__(SNT) void topn_rows_kernel(const uint32_t *__restrict__ keys, int Vs,
                                                         int V, const int32_t *__restrict__ row_ptr,
                                                         int amount, int A,
@@ -276,21 +300,7 @@ __global__ __launch_bounds__(SNT) void topn_rows_kernel(const uint32_t *__restri
   while (P < want) P <<= 1;
   for (int i = min(s_cnt, want) + tid; i < P; i += SNT) sel[i] = 0ull;  // below every candidate
   __syncthreads();
-  for (int size = 2; size <= P; size <<= 1)
-    for (int stride = size >> 1; stride > 0; stride >>= 1) {
-      for (int i = tid; i < P; i += SNT) {
-        const int pr = i ^ stride;
-        if (pr > i) {
-          const bool down = (i & size) == 0;
-          const uint64_t a = sel[i], b = sel[pr];
-          if ((a < b) == down) {
-            sel[i] = b;
-            sel[pr] = a;
-          }
-        }
-      }
-      __syncthreads();
-    }
+  bitonic_sort_desc(sel, P);
   for (int i = tid; i < want; i += SNT) {
     const uint64_t cmp = sel[i];
     adds[i] = (int32_t)(uint32_t)cmp;
@@ -310,11 +320,11 @@ __device__ __forceinline__ uint64_t rank_load(const uint32_t *k, const uint64_t 
                                                int i) {
   return pass == 0 ? ((uint64_t)k[i] << 32) | (uint32_t)i : src[i];
 }
-// the valid lanes of the wave that hold digit dg
-__device__ __forceinline__ uint64_t rank_match(uint32_t dg, bool valid) {
+// the valid lanes of the wave that hold digit dg (a value below 2^nbits)
+__device__ __forceinline__ uint64_t rank_match(uint32_t dg, bool valid, int nbits = tiles::BITS) {
   uint64_t m = __ballot(valid);
 #pragma unroll
-  for (int bit = 0; bit < tiles::BITS; ++bit) {
+  for (int bit = 0; bit < nbits; ++bit) {
     const bool b = (dg >> bit) & 1u;
     const uint64_t bb = __ballot(b);
     m &= b ? bb : ~bb;
@@ -423,6 +433,160 @@ __global__ __launch_bounds__(SNT) void rank_rows_kernel(const uint32_t *__restri
     }
     __threadfence_block();
     __syncthreads();
+  }
+}
+
+// Position of chosen cards in a row's ranking without sorting the row: the rank of target t is the
+// number of candidates (key' != 0) whose composite (key' << 32 | card) is above t's.  One workgroup
+// per row; up to TCH of the row's targets at a time:
+//   stage : the targets' composites into LDS (0 for a target outside [0, V) or inside the cube:
+//           below every candidate, so it sorts behind the Tv valid ones), bitonic sort, descending.
+//   count : the row's keys are streamed once with 16-byte loads.  A candidate x at or below the
+//           smallest target composite beats no target and is dropped after one comparison (with a
+//           useful model that is nearly every card).  Otherwise g = #{targets >= x} (binary
+//           search) and x is above exactly the sorted targets p >= g: cnt[g] += 1, the lanes of a
+//           wave that share g adding once between them (ballot match on the bits of g) — with few
+//           targets most of a wave lands on one counter.
+//   scan  : the rank of sorted target p is the inclusive prefix sum of cnt over g <= p.
+//   write : every target looks its composite up in the sorted chunk (duplicates find the same
+//           first position) and takes that rank; results go to the target's own slot.
+// More targets than TCH: further chunks over the same keys (L2-resident).  The hit counters are
+// summed per thread, reduced in LDS and added with one atomic per workgroup and counter.
+constexpr int TCH = 2048;     // targets per chunk: 16 KB of composites + 8 KB of counts
+constexpr int MAX_CUTOFFS = 8;
+
+// (8 waves per SIMD = two workgroups per CU: without the attribute the cut-offs and pointers
+// take 101 SGPRs, one too many)
+__global__ __launch_bounds__(SNT) __attribute__((amdgpu_waves_per_eu(8, 8))) void target_ranks_kernel(
+    const uint32_t *__restrict__ keys, int Vs, int V, const int32_t *__restrict__ tgt_ptr,
+    const int32_t *__restrict__ tgt, const int32_t *__restrict__ cutoffs, int n_cut,
+    int32_t *__restrict__ ranks, float *__restrict__ tgt_vals, unsigned long long *__restrict__ hits) {
+  static_assert(TCH == 2 * SNT, "the scan gives every thread two counters");
+  __shared__ uint64_t srt[TCH];
+  __shared__ uint32_t cnt[TCH];
+  __shared__ int wtot[SNT / 64];
+  __shared__ uint32_t s_hit[MAX_CUTOFFS + 1];
+  __shared__ int s_best;
+  const int tid = threadIdx.x, lane = tid & 63;
+  const uint64_t lt = (1ull << lane) - 1ull;
+  const int r = blockIdx.x;
+  const int tbeg = tgt_ptr[r], T = tgt_ptr[r + 1] - tbeg;
+  if (T <= 0) return;  // (block-uniform) nothing to rank, nothing to count
+  const uint32_t *k = keys + (int64_t)r * Vs;
+  int cut[MAX_CUTOFFS];
+#pragma unroll
+  for (int c = 0; c < MAX_CUTOFFS; ++c) cut[c] = (hits && c < n_cut) ? cutoffs[c] : 0;
+  uint32_t hit[MAX_CUTOFFS], nvalid = 0;
+#pragma unroll
+  for (int c = 0; c < MAX_CUTOFFS; ++c) hit[c] = 0u;
+  int best = 0x7FFFFFFF;
+  const int steps = (int)cdiv(V, 4 * SNT);  // the same trip count for every lane: ballots inside
+
+  for (int cb = 0; cb < T; cb += TCH) {
+    const int Tc = min(TCH, T - cb);
+    int P = 1, nbits = 0;
+    while (P < Tc) P <<= 1, ++nbits;
+    const int32_t *tg = tgt + tbeg + cb;
+    for (int i = tid; i < P; i += SNT) {
+      uint64_t x = 0ull;
+      if (i < Tc) {
+        const int t = tg[i];
+        if ((uint32_t)t < (uint32_t)V) {  // never index with an id outside the row
+          const uint32_t key = k[t];
+          if (key) x = ((uint64_t)key << 32) | (uint32_t)t;
+        }
+      }
+      srt[i] = x;
+      cnt[i] = 0u;
+    }
+    __syncthreads();
+    bitonic_sort_desc(srt, P);
+    int Tv = 0;  // valid targets: the first position holding 0
+    for (int hi = P; Tv < hi;) {
+      const int mid = (Tv + hi) >> 1;
+      if (srt[mid] != 0ull) Tv = mid + 1; else hi = mid;
+    }
+    if (Tv > 0) {
+      const uint64_t low = srt[Tv - 1];
+      for (int st = 0; st < steps; ++st) {
+        const int base = 4 * (st * SNT + tid);
+        uint4 kk = make_uint4(0u, 0u, 0u, 0u);
+        if (base < V) kk = *reinterpret_cast<const uint4 *>(k + base);  // base + 3 < Vs
+        const uint32_t ke[4] = {kk.x, kk.y, kk.z, kk.w};
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+          const uint64_t x = ((uint64_t)ke[e] << 32) | (uint32_t)(base + e);
+          const bool above = base + e < V && ke[e] != 0u && x > low;
+          if (__ballot(above) == 0ull) continue;  // (wave-uniform)
+          int g = 0;  // first position with srt[g] < x; above: g < Tv
+          if (above)
+            for (int hi = Tv - 1; g < hi;) {
+              const int mid = (g + hi) >> 1;
+              if (srt[mid] >= x) g = mid + 1; else hi = mid;
+            }
+          const uint64_t m = rank_match((uint32_t)g, above, nbits);
+          if (above && (m & lt) == 0ull) atomicAdd(&cnt[g], (uint32_t)__popcll(m));
+        }
+      }
+    }
+    __syncthreads();
+    {  // inclusive prefix sums in place; thread tid owns counters 2 tid and 2 tid + 1
+      const int c0 = 2 * tid < P ? (int)cnt[2 * tid] : 0;
+      const int c1 = 2 * tid + 1 < P ? (int)cnt[2 * tid + 1] : 0;
+      const int incl = block_incl_scan(c0 + c1, wtot);
+      if (2 * tid < P) cnt[2 * tid] = (uint32_t)(incl - c1);
+      if (2 * tid + 1 < P) cnt[2 * tid + 1] = (uint32_t)incl;
+    }
+    __syncthreads();
+    for (int i = tid; i < Tc; i += SNT) {
+      const int t = tg[i];
+      uint32_t key = 0u;
+      if ((uint32_t)t < (uint32_t)V) key = k[t];
+      int rank = -1;
+      float val = 0.f;
+      if (key) {
+        const uint64_t x = ((uint64_t)key << 32) | (uint32_t)t;
+        int p = 0;  // first position with srt[p] <= x: x itself
+        for (int hi = Tv - 1; p < hi;) {
+          const int mid = (p + hi) >> 1;
+          if (srt[mid] > x) p = mid + 1; else hi = mid;
+        }
+        rank = (int)cnt[p];
+        val = __uint_as_float(key - 1u);
+        ++nvalid;
+        best = min(best, rank);
+#pragma unroll
+        for (int c = 0; c < MAX_CUTOFFS; ++c) hit[c] += rank < cut[c] ? 1u : 0u;
+      }
+      ranks[tbeg + cb + i] = rank;
+      tgt_vals[tbeg + cb + i] = val;
+    }
+    __syncthreads();  // srt and cnt are free for the next chunk
+  }
+
+  if (!hits) return;
+  if (tid <= MAX_CUTOFFS) s_hit[tid] = 0u;
+  if (tid == 0) s_best = 0x7FFFFFFF;
+  __syncthreads();
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) {
+#pragma unroll
+    for (int c = 0; c < MAX_CUTOFFS; ++c) hit[c] += __shfl_xor(hit[c], off);
+    nvalid += __shfl_xor(nvalid, off);
+    best = min(best, __shfl_xor(best, off));
+  }
+  if (lane == 0 && nvalid) {
+#pragma unroll
+    for (int c = 0; c < MAX_CUTOFFS; ++c)
+      if (hit[c]) atomicAdd(&s_hit[c], hit[c]);
+    atomicAdd(&s_hit[MAX_CUTOFFS], nvalid);
+    atomicMin(&s_best, best);
+  }
+  __syncthreads();
+  if (tid < n_cut && s_hit[tid]) atomicAdd(hits + tid, (unsigned long long)s_hit[tid]);
+  if (tid == n_cut && s_hit[MAX_CUTOFFS]) {
+    atomicAdd(hits + n_cut, (unsigned long long)s_hit[MAX_CUTOFFS]);  // targets counted
+    if (n_cut > 0 && s_best < cut[0]) atomicAdd(hits + n_cut + 1, 1ull);  // the row's best is a hit
   }
 }
 
@@ -551,5 +715,38 @@ extern "C" int cc_recommend_batch_rank_fp32(const float *params, int32_t V, int3
                      w.Vs, V, row_ptr, amount, A, pa, pb, (int)rank_pitch(V), n_add, additions,
                      add_vals);
   CC_LAUNCH_CHECK("rank_rows_kernel");
+  return CC_OK;
+}
+
+// Ranks of chosen cards: the shared chain leaves the keys in the batch workspace (nothing more is
+// needed: no ping-pong buffers, no R x V result), then one counting workgroup per row.
+extern "C" size_t cc_recommend_batch_target_ranks_ws_size(int32_t V, int32_t d, int32_t R,
+                                                          int32_t max_n) {
+  return batch_ws(V, d, R, max_n).total + 256;
+}
+
+extern "C" int cc_recommend_batch_target_ranks_fp32(
+    const float *params, int32_t V, int32_t d, int32_t R, const int32_t *row_ptr,
+    const int32_t *idx, int32_t max_n, const int32_t *tgt_ptr, const int32_t *tgt,
+    const int32_t *cutoffs, int32_t n_cutoffs, void *ws, int32_t *ranks, float *tgt_vals,
+    unsigned long long *hits, float *cut_vals, float *probs, void *stream) {
+  CC_REQUIRE(params && row_ptr && idx && tgt_ptr && tgt && ws && ranks && tgt_vals && cut_vals,
+             "cc_recommend_batch_target_ranks_fp32: null pointer");
+  CC_REQUIRE(V > 0 && R >= 0 && max_n >= 0 && max_n <= V,
+             "cc_recommend_batch_target_ranks_fp32: V/R/max_n");
+  if (int rc = cc::infer_check_d(d, "cc_recommend_batch_target_ranks_fp32")) return rc;
+  CC_REQUIRE(n_cutoffs >= 0 && n_cutoffs <= MAX_CUTOFFS && (n_cutoffs == 0 || cutoffs),
+             "cc_recommend_batch_target_ranks_fp32: n_cutoffs outside 0..8, or cutoffs null");
+  CC_REQUIRE(((uintptr_t)ws & 255) == 0,
+             "cc_recommend_batch_target_ranks_fp32: ws must be 256-byte aligned");
+  if (R == 0) return CC_OK;
+  const BatchWs w = batch_ws(V, d, R, max_n);
+  hipStream_t s = as_stream(stream);
+  if (int rc = batch_keys_launch(params, V, d, R, row_ptr, idx, max_n, ws, w, cut_vals, probs, s))
+    return rc;
+  hipLaunchKernelGGL(target_ranks_kernel, dim3(R), dim3(SNT), 0, s,
+                     (const uint32_t *)((char *)ws + w.keys), w.Vs, V, tgt_ptr, tgt, cutoffs,
+                     n_cutoffs, ranks, tgt_vals, hits);
+  CC_LAUNCH_CHECK("target_ranks_kernel");
   return CC_OK;
 }

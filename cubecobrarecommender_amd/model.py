@@ -218,6 +218,12 @@ class CC_Recommender:
         """The resident single-cube recommend engine (fp32 forward + GPU top-N)."""
         return self._rec()
 
+    def evaluate_holdout(self, cubes, **kw):
+        """Held-out ranking metrics (recall@K, NDCG@K, hit rate@K, MRR) of the current weights on
+        `cubes` (card-index lists): evaluate.evaluate_holdout through the resident recommender."""
+        from .evaluate import evaluate_holdout
+        return evaluate_holdout(self.recommender(), cubes, **kw)
+
 
 def load_model(path, dtype='fp32'):
     """keras.models.load_model('ml_files/<name>') (ml_recommend.py:54, ml_recommend_web.py:37)."""

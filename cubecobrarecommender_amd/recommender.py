@@ -59,6 +59,33 @@ def pack_cubes(cubes, V):
     return row_ptr, idx, int(counts.max()) if R else 0, inputs, slot
 
 
+def pack_targets(targets, inputs, V):
+    """R target-card lists -> the target CSR of cc_recommend_batch_target_ranks_fp32 (pure host
+    code).  inputs[r] is the visible cube of row r (as pack_cubes returns it).
+
+    Returns (tgt_ptr int32 [R+1], tgt int32 [tgt_ptr[R]]): row r holds targets[r] in the caller's
+    order, duplicates kept.  Raises ValueError for a target outside [0, V), and for a target that
+    is also a card of its row's cube (it has no rank among the candidates), naming the cube."""
+    tl = [np.asarray(t, np.int64).reshape(-1) for t in targets]
+    R = len(tl)
+    if R != len(inputs):
+        raise ValueError(f'{R} target lists for {len(inputs)} cubes')
+    check_card_ids(tl, V)
+    lens = np.fromiter((len(t) for t in tl), np.int64, R)
+    flat = np.concatenate(tl) if R else np.zeros(0, np.int64)
+    rows = np.repeat(np.arange(R, dtype=np.int64), lens)
+    cube_lens = np.fromiter((len(ci) for ci in inputs), np.int64, R)
+    cube_key = np.repeat(np.arange(R, dtype=np.int64), cube_lens) * V + (
+        np.concatenate(inputs).astype(np.int64) if R else np.zeros(0, np.int64))
+    inside = np.isin(rows * V + flat, cube_key)
+    if inside.any():
+        at = int(np.flatnonzero(inside)[0])
+        raise ValueError(f'cube {int(rows[at])}: target card {int(flat[at])} is in the cube')
+    tgt_ptr = np.zeros(R + 1, np.int32)
+    tgt_ptr[1:] = np.cumsum(lens)
+    return tgt_ptr, flat.astype(np.int32)
+
+
 def cuts_in_input_order(cut_csr, slot, inputs):
     """cut_csr (aligned with the CSR's idx) -> per cube, the values in the caller's input order
     with duplicates repeated (pure host code)."""
@@ -281,6 +308,83 @@ class Recommender:
                 pending = queued
             collect(*pending)
         return out
+
+    # ------------------------------------------------------------------ held-out evaluation
+    def target_ranks(self, cubes, targets, cutoffs=(), rows_per_launch=512):
+        """Where the cards of targets[r] land in the ranking `recommend_many(cubes, <all>)` gives
+        cube r, without ranking anything (cc_recommend_batch_target_ranks_fp32: the batched
+        forward, then one counting workgroup per row; nothing of size R x V comes back).
+
+        Returns (ranks, vals, hits): per cube an int32 array of 0-based positions in `additions`
+        and a float32 array of the targets' probabilities, both in the caller's target order
+        (duplicates kept); hits is None without cutoffs, else the device-side counters as a
+        uint64 array [len(cutoffs) + 2]: targets with rank < cutoffs[k] for each k, then the
+        targets counted, then the cubes whose best target has rank < cutoffs[0].  Up to 8
+        cutoffs.  An id outside [0, V) in either list, or a target that is also in its cube,
+        raises ValueError before anything is launched."""
+        rows_per_launch = max(1, int(rows_per_launch))
+        cutoffs = [int(k) for k in cutoffs]
+        if len(cutoffs) > 8:
+            raise ValueError('at most 8 cutoffs')
+        inputs = [np.asarray(c, np.int64).reshape(-1) for c in cubes]
+        R = len(inputs)
+        V, d, dev = self.V, self.d, self.dev
+        check_card_ids(inputs, V)
+        tgt_ptr, tgt = pack_targets(targets, inputs, V)
+        nk = len(cutoffs)
+        if R == 0:
+            return [], [], (np.zeros(nk + 2, np.uint64) if nk else None)
+        ws_size = L.lib().cc_recommend_batch_target_ranks_ws_size
+        ranks, vals = [], []
+
+        def launch(r0, r1):
+            """Pack rows r0..r1, queue their launch and the copies of its results to pinned
+            memory; no waiting."""
+            row_ptr, idx, max_n, _, _ = pack_cubes(inputs[r0:r1], V)
+            Rc, nnz = r1 - r0, len(idx)
+            t0, t1 = int(tgt_ptr[r0]), int(tgt_ptr[r1])
+            tp = tgt_ptr[r0:r1 + 1] - tgt_ptr[r0]
+            nt = t1 - t0
+            need = int(ws_size(V, d, Rc, max_n)) // 4 + 64
+            if getattr(self, '_batch_ws', None) is None or self._batch_ws.numel() < need:
+                self._batch_ws = torch.empty(need, device=dev, dtype=torch.int32)   # grown when needed, kept
+            rp_d = torch.from_numpy(row_ptr).to(dev, non_blocking=True)
+            ix_d = torch.from_numpy(idx if nnz else np.zeros(1, np.int32)).to(dev, non_blocking=True)
+            tp_d = torch.from_numpy(tp).to(dev, non_blocking=True)
+            tg_d = torch.from_numpy(tgt[t0:t1] if nt else np.zeros(1, np.int32)).to(dev, non_blocking=True)
+            rk = torch.empty(max(nt, 1), device=dev, dtype=torch.int32)
+            tv = torch.empty(max(nt, 1), device=dev, dtype=torch.float32)
+            cuts = torch.empty(max(nnz, 1), device=dev, dtype=torch.float32)   # the chain's; not returned
+            L.call('cc_recommend_batch_target_ranks_fp32', L.ptr(self.params), V, d, Rc, L.ptr(rp_d),
+                   L.ptr(ix_d), max_n, L.ptr(tp_d), L.ptr(tg_d), L.ptr(cut_d), nk, L.ptr(self._batch_ws),
+                   L.ptr(rk), L.ptr(tv), L.ptr(hits_d), L.ptr(cuts), None, L.stream_ptr(self.stream))
+            host = [torch.empty(t.shape, dtype=t.dtype, pin_memory=True).copy_(t, non_blocking=True)
+                    for t in (rk, tv)]
+            done = torch.cuda.Event()
+            done.record(self.stream)
+            return r0, r1, host, done
+
+        def collect(r0, r1, host, done):
+            done.synchronize()
+            rk, tv = host[0].numpy(), host[1].numpy()
+            base = int(tgt_ptr[r0])
+            for r in range(r0, r1):
+                lo, hi = int(tgt_ptr[r]) - base, int(tgt_ptr[r + 1]) - base
+                ranks.append(rk[lo:hi].copy())
+                vals.append(tv[lo:hi].copy())
+
+        with self.lock, torch.cuda.stream(self.stream):
+            cut_d = torch.tensor(cutoffs, device=dev, dtype=torch.int32) if nk else None
+            hits_d = torch.zeros(nk + 2, device=dev, dtype=torch.int64) if nk else None
+            pending = None      # a launch's results are unpacked while the next one runs
+            for r0 in range(0, R, rows_per_launch):
+                queued = launch(r0, min(R, r0 + rows_per_launch))
+                if pending is not None:
+                    collect(*pending)
+                pending = queued
+            collect(*pending)
+            hits = hits_d.cpu().numpy().view(np.uint64) if nk else None
+        return ranks, vals, hits
 
     def _full_order(self, probs, uniq, amount):
         """The complete ranking (cc_topn with `order`; tests and tools only)."""

@@ -743,6 +743,35 @@ int cc_recommend_batch_rank_fp32(const float *params, int32_t V, int32_t d, int3
                                  int32_t amount, void *ws, int32_t *n_add, int32_t *additions,
                                  float *add_vals, float *cut_vals, float *probs, void *stream);
 
+/* Held-out evaluation: where do chosen target cards land in each row's ranking?  The same chain
+ * up to the rows' sort keys, then one workgroup per row COUNTS instead of sorting: no ping-pong
+ * buffers, no R x V result.  Arguments and preconditions of the visible cubes (row_ptr, idx,
+ * max_n), cut_vals and probs are those of cc_recommend_batch_fp32.
+ *   tgt_ptr [R + 1], tgt: CSR of the rows' target cards (device); any order, duplicates allowed,
+ *   any number per row.  With key'(c) = in_cube(c) ? 0 : float_bits(p_c) + 1 and the composite
+ *   (key'(c) << 32) | c, target t of row r gets
+ *     ranks    = #{ c : key'(c) != 0 and composite(c) > composite(t) }: t's 0-based position in
+ *                additions of cc_recommend_batch_rank_fp32 on that row (descending probability,
+ *                equal probabilities higher card index first); duplicates get the same rank;
+ *     tgt_vals = p_t, the bits probs[r][t] would hold.
+ *   A target outside [0, V) or inside the row's cube is invalid: ranks = -1, tgt_vals = 0, counted
+ *   nowhere (and never used as an index).  ranks / tgt_vals [tgt_ptr[R]] are aligned with tgt.
+ *   cutoffs: device array of n_cutoffs (0..8) K values, NULL when n_cutoffs == 0.
+ *   hits [n_cutoffs + 2] or NULL, zeroed by the caller; the call ADDS, per valid target,
+ *   hits[k] += rank < cutoffs[k] and hits[n_cutoffs] += 1, and hits[n_cutoffs + 1] += 1 per row
+ *   whose best valid target has rank < cutoffs[0] (never with n_cutoffs == 0).  Integer atomics,
+ *   one per workgroup and counter: the totals do not depend on the order.
+ *   ws: cc_recommend_batch_target_ranks_ws_size(V, d, R, max_n) bytes, 256-B aligned; the call
+ *   does not depend on its contents.  R == 0 returns CC_OK without a launch.
+ * CC_ERR_ARG: null pointer, max_n > V, d not a multiple of 64 in [64, 1024], n_cutoffs outside
+ * 0..8, unaligned ws. */
+size_t cc_recommend_batch_target_ranks_ws_size(int32_t V, int32_t d, int32_t R, int32_t max_n);
+int cc_recommend_batch_target_ranks_fp32(
+    const float *params, int32_t V, int32_t d, int32_t R, const int32_t *row_ptr,
+    const int32_t *idx, int32_t max_n, const int32_t *tgt_ptr, const int32_t *tgt,
+    const int32_t *cutoffs, int32_t n_cutoffs, void *ws, int32_t *ranks, float *tgt_vals,
+    unsigned long long *hits, float *cut_vals, float *probs, void *stream);
+
 /* ---------------------------------------------------------------- card co-occurrence graph (N1)
  * Replaces src/non_ml/utils.py:75-91 (create_adjacency_matrix, called by
  * src/non_ml/create_mtx.py:19) and the M~ normalisation of src/ml/train.py:69-71.

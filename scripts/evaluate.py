@@ -1,0 +1,48 @@
+#!/usr/bin/env python3
+"""Held-out evaluation of a saved model: `evaluate.py name [K ...]` (K defaults to 10 50 100).
+
+Loads ml_files/<name> with load_model and the cubes the way scripts/train.py does
+(data/maps/nameToId.json + data/cube/*.json, or --synthetic C V with the same seed argument), hides
+--hide of every cube's cards, ranks the hidden ones on the GPU and prints one JSON line:
+recall@K, ndcg@K, hit_rate@K for each K, mrr, n_cubes, n_targets, hits (the device's counters)."""
+import argparse
+import json
+import os
+import sys
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+
+
+def main(argv=None):
+    ap = argparse.ArgumentParser()
+    ap.add_argument('name')
+    ap.add_argument('ks', nargs='*', type=int, default=[10, 50, 100])
+    ap.add_argument('--hide', type=float, default=0.2, help='fraction below 1, or a count')
+    ap.add_argument('--seed', type=int, default=0)
+    ap.add_argument('--synthetic', nargs=2, type=int, metavar=('C', 'V'))
+    ap.add_argument('--data-dir', default='./data')
+    ap.add_argument('--out-dir', default='./ml_files')
+    a = ap.parse_args(argv)
+    from cubecobrarecommender_amd import data as D
+    from cubecobrarecommender_amd.evaluate import evaluate_holdout
+    from cubecobrarecommender_amd.model import load_model
+    from cubecobrarecommender_amd.synthetic import synthetic_cubes
+    model = load_model(os.path.join(a.out_dir, a.name))
+    if a.synthetic:
+        C, V = a.synthetic
+        indptr, idx = synthetic_cubes(C, V, seed=a.seed)
+    else:
+        V, name_lookup, card_to_int, _ = D.get_card_maps(os.path.join(a.data_dir, 'maps', 'nameToId.json'))
+        indptr, idx = D.lists_to_csr(D.build_cube_lists(os.path.join(a.data_dir, 'cube'), name_lookup, card_to_int))
+    if V != model.N:
+        raise SystemExit(f'the model has {model.N} cards, the data {V}')
+    cubes = [idx[indptr[c]:indptr[c + 1]] for c in range(len(indptr) - 1)]
+    hide = int(a.hide) if a.hide >= 1 else a.hide
+    out = evaluate_holdout(model, cubes, ks=a.ks or [10, 50, 100], hide=hide, seed=a.seed)
+    out = {'name': a.name, 'cubes': len(cubes), 'hide': hide, 'seed': a.seed, **out}
+    print(json.dumps(out))
+    return out
+
+
+if __name__ == '__main__':
+    main()
