@@ -208,6 +208,8 @@ SIGNATURES = {
     'cc_recommend_batch_target_ranks_ws_size': (_SZ, [_I32, _I32, _I32, _I32]),
     'cc_recommend_batch_target_ranks_fp32': (C.c_int, [_P, _I32, _I32, _I32, _P, _P, _I32, _P, _P, _P, _I32, _P,
                                                        _P, _P, _P, _P, _P, _P]),
+    'cc_recommend_batch_loss_ws_size': (_SZ, [_I32, _I32, _I32, _I32]),
+    'cc_recommend_batch_loss_fp32': (C.c_int, [_P, _I32, _I32, _I32, _P, _P, _I32, _P, _P, _P, _P, _P, _P]),
     'cc_adjacency_ws_size': (_SZ, [_I32, _I32, _I32, _I32]),
     'cc_adjacency': (C.c_int, [_P, _P, _I32, _I32, _I32, _P, _P, _P, _P, _P, _P]),
 }

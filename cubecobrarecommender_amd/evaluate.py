@@ -4,6 +4,10 @@ and ask where the hidden cards land in its ranking.
 Pure host code except the one call of Recommender.target_ranks, which returns every hidden card's
 exact position in the ranking `recommend_many(visible, <all>)` would give, without ranking anything
 (cc_recommend_batch_target_ranks_fp32).  The metrics are float64 functions of those integers.
+
+evaluate_loss is the other held-out number, the training loss on cubes the model did not train on:
+Recommender.reconstruction_loss (cc_recommend_batch_loss_fp32) reduces every row's binary
+cross-entropy and argmax on the device, the host takes the means.
 """
 import numpy as np
 
@@ -78,6 +82,31 @@ def metrics_from_ranks(ranks, ks):
     out['n_cubes'] = n_cubes
     out['n_targets'] = n_targets
     return out
+
+
+def evaluate_loss(model, cubes, targets=None, rows_per_launch=512):
+    """The reconstruction output's loss and accuracy on `cubes` (clean inputs; targets=None means
+    the cubes themselves) -> {'bce', 'output_1_accuracy', 'n_cubes'}: what Keras' model.evaluate
+    reports for output 1.  `model` is a CC_Recommender or a Recommender; the per-row reduction
+    runs on the device (Recommender.reconstruction_loss).
+
+      bce                mean over the cubes of the row losses (float64 sum / R)
+      output_1_accuracy  categorical accuracy: the share of rows whose most probable card (first
+                         index on ties) is the row's first (lowest) target id, 0 for a row without
+                         targets - tf.argmax of the multi-hot row"""
+    rec = model.recommender() if hasattr(model, 'recommender') else model
+    cubes = list(cubes)
+    row_loss, row_pred = rec.reconstruction_loss(cubes, targets, rows_per_launch=rows_per_launch)
+    R = len(cubes)
+    if R == 0:
+        return {'bce': 0.0, 'output_1_accuracy': 0.0, 'n_cubes': 0}
+    first = np.zeros(R, np.int64)
+    for r, t in enumerate(cubes if targets is None else targets):
+        t = np.asarray(t, np.int64).reshape(-1)
+        first[r] = t.min() if len(t) else 0
+    hits = int(np.count_nonzero(np.asarray(row_pred, np.int64) == first))
+    return {'bce': float(np.sum(np.asarray(row_loss, np.float64))) / R, 'output_1_accuracy': hits / R,
+            'n_cubes': R}
 
 
 def evaluate_holdout(model, cubes, ks=(10, 50, 100), hide=0.2, seed=0, min_visible=1, rows_per_launch=512):

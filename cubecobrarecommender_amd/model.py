@@ -94,6 +94,7 @@ class CC_Recommender:
         self.lr = 1e-3
         self.trainer = None
         self._recommender = None
+        self._val_rec = None      # fit(validation_data): the recommender the epochs' weights go into
         self.encoder = _Encoder(self)
         self.decoder = _Decoder(self)
         self.history = []
@@ -120,11 +121,32 @@ class CC_Recommender:
         self.reg = float(loss_weights[1])
         self.lr = float(learning_rate)
 
-    def fit(self, generator, epochs=1, verbose=1, rank=0, world=1, graphs=True, log=print):
+    def fit(self, generator, epochs=1, verbose=1, rank=0, world=1, graphs=True, log=print,
+            validation_data=None, validation_ks=()):
         """Keras ``fit(generator, epochs)`` (train.py:99-102).  The optimizer state persists across
         calls like Keras' (optimizer.iterations and the m/v slots): a second fit() resumes Adam's
         step count and moments, and the device step counter keeps the Philox noise draws fresh.
-        The logged loss is the epoch mean over its batches, as Keras' progress bar reports it."""
+        The logged loss is the epoch mean over its batches, as Keras' progress bar reports it.
+
+        validation_data: a list of cubes (card-index lists or a dense 0/1 matrix; the targets are
+        the cubes themselves) or a tuple (x_cubes, y_cubes).  After every epoch the reconstruction
+        output is evaluated on it with that epoch's weights (evaluate_loss: the fp32 master weights
+        go through the host into a resident Recommender, once per epoch), and 'val_bce' and
+        'val_output_1_accuracy' join the epoch's history entry and log line.  The inputs are always
+        clean: the Philox noise lives in the trainer only, so these are the numbers of
+        ``evaluate`` and not of a noised batch.  validation_ks adds evaluate_holdout's
+        'val_recall@K' for each K and 'val_mrr' (on the x cubes).  Validation draws nothing and
+        writes no training state: the parameters, m, v and the step count after fit() are those
+        without it.  The regulariser (output 2) has no held-out version and is not evaluated.
+        Data parallel (world > 1) with validation_data raises ValueError: evaluate after fit()."""
+        if validation_data is not None and world > 1:
+            raise ValueError('validation_data needs world == 1: a data-parallel run evaluates after fit()')
+        val = None
+        if validation_data is not None:
+            pair = isinstance(validation_data, tuple) and len(validation_data) == 2
+            val = (_rows_of(validation_data[0]), _rows_of(validation_data[1])) if pair else \
+                (_rows_of(validation_data), None)
+            validation_ks = [int(k) for k in validation_ks]
         from .trainer import TrainConfig, Trainer
         cfg = TrainConfig(V=self.N, d=self.d, batch_size=generator.batch_size, reg=self.reg,
                           noise=generator.noise, noise_std=generator.noise_std, lr=self.lr,
@@ -175,12 +197,16 @@ class CC_Recommender:
             # output's loss — written into the checkpoint with the optimizer state
             n = float(steps * cfg.batch_size * world)
             self._metrics = {'loss': (l['loss'] * n, n), 'output_1_loss': (l['bce'] * n, n)}
+            dt = time.perf_counter() - t0      # the training steps alone: validation is not in the rate
+            if val is not None:
+                l.update(self._validate(tr, val, validation_ks))
             if verbose and rank == 0:
-                dt = time.perf_counter() - t0
                 acc = ''.join(f' - {k}: {l[k]:.4f}' for k in ('output_1_accuracy', 'output_2_accuracy') if k in l)
+                acc += ''.join(f' - {k}: {v:.6f}' for k, v in l.items() if k.startswith('val_'))
                 log(f'Epoch {ep + 1}/{epochs} - {steps} steps - {dt:.3f}s - loss: {l["loss"]:.6f} '
                     f'- bce: {l["bce"]:.6f} - kl: {l["kl"]:.6f}{acc} - {steps * cfg.batch_size * world / dt:.0f} cubes/s')
 
+        self._val_rec = None
         tr.flush()
         if getattr(tr, 'sharded', None) is not None:   # data parallel: m, v are sharded — gather
             tr.sharded.gather_state()                   # them here, on every rank (collective)
@@ -190,6 +216,41 @@ class CC_Recommender:
         self._recommender = None
         self._step = int(tr.state[0].item())
         return self
+
+    def _validate(self, tr, val, ks):
+        """fit()'s per-epoch validation: the trainer's fp32 master weights, in the standard layout,
+        into a Recommender kept for the fit -> the 'val_*' entries of the epoch."""
+        from .evaluate import evaluate_holdout, evaluate_loss
+        tr.flush()
+        flat = tr.standard(tr.params)
+        if self._val_rec is None:
+            self._val_rec = Recommender(flat, self.N, self.d)
+        else:
+            rec = self._val_rec
+            with rec.lock:
+                rec.params.copy_(torch.as_tensor(flat[:rec.params.numel()], dtype=torch.float32))
+                torch.cuda.synchronize(rec.dev)    # the launches run on the recommender's own stream
+        x, y = val
+        e = evaluate_loss(self._val_rec, x, y)
+        out = {'val_bce': e['bce'], 'val_output_1_accuracy': e['output_1_accuracy']}
+        if ks:
+            h = evaluate_holdout(self._val_rec, x, ks=ks)
+            out.update({f'val_recall@{K}': h[f'recall@{K}'] for K in ks})
+            out['val_mrr'] = h['mrr']
+        return out
+
+    def evaluate(self, x, y=None, batch_size=512, verbose=0):
+        """Keras ``model.evaluate`` for the reconstruction output on the current weights ->
+        {'bce', 'output_1_accuracy', 'n_cubes'} (evaluate.evaluate_loss; the per-row loss and
+        argmax are reduced on the device in launches of batch_size rows).  x / y: dense 0/1
+        matrices or lists of card-index lists; y=None means x.  The inputs are taken as they
+        are: no noise is drawn."""
+        from .evaluate import evaluate_loss
+        out = evaluate_loss(self.recommender(), _rows_of(x), None if y is None else _rows_of(y),
+                            rows_per_launch=batch_size)
+        if verbose:
+            print(f"{out['n_cubes']} cubes - bce: {out['bce']:.6f} - output_1_accuracy: {out['output_1_accuracy']:.4f}")
+        return out
 
     def save(self, dest, save_format='tf'):
         """model.save(dest, save_format='tf') (train.py:112-115).  No collectives: fit() already

@@ -386,6 +386,78 @@ class Recommender:
             hits = hits_d.cpu().numpy().view(np.uint64) if nk else None
         return ranks, vals, hits
 
+    # ------------------------------------------------------------------ validation loss
+    def reconstruction_loss(self, cubes, targets=None, rows_per_launch=512):
+        """The reconstruction output's loss of every cube, reduced per row on the device
+        (cc_recommend_batch_loss_fp32: the batched forward of `recommend_many`, then the output
+        tile with a loss epilogue; nothing of size R x V is written or copied back).
+
+        Returns (row_loss float64 [R], row_pred int32 [R]): row r's binary cross-entropy of the
+        logits of cubes[r] against the multi-hot row of targets[r] (mean over the V cards, fp64
+        terms from the fp32 logits, summed in a fixed order: a row's bits do not depend on R or
+        on the launch it falls into), and the first index of its largest probability (Keras'
+        categorical accuracy compares it with the first target).  targets=None means the cubes
+        themselves.  Duplicates collapse in both lists; an id outside [0, V) in either raises
+        ValueError before anything is launched."""
+        rows_per_launch = max(1, int(rows_per_launch))
+        inputs = [np.asarray(c, np.int64).reshape(-1) for c in cubes]
+        R = len(inputs)
+        V, d, dev = self.V, self.d, self.dev
+        check_card_ids(inputs, V)
+        if targets is None:
+            tgts = inputs
+        else:
+            tgts = [np.asarray(t, np.int64).reshape(-1) for t in targets]
+            if len(tgts) != R:
+                raise ValueError(f'{len(tgts)} target lists for {R} cubes')
+            check_card_ids(tgts, V)
+        row_loss, row_pred = np.zeros(R, np.float64), np.zeros(R, np.int32)
+        if R == 0:
+            return row_loss, row_pred
+        ws_size = L.lib().cc_recommend_batch_loss_ws_size
+
+        def launch(r0, r1):
+            """Pack rows r0..r1, queue their launch and the copies of its results to pinned
+            memory; no waiting."""
+            row_ptr, idx, max_n, _, _ = pack_cubes(inputs[r0:r1], V)
+            tgt_ptr, tgt = (row_ptr, idx) if targets is None else pack_cubes(tgts[r0:r1], V)[:2]
+            Rc = r1 - r0
+            need = int(ws_size(V, d, Rc, max_n)) // 4 + 64
+            if getattr(self, '_batch_ws', None) is None or self._batch_ws.numel() < need:
+                self._batch_ws = torch.empty(need, device=dev, dtype=torch.int32)   # grown when needed, kept
+            rp_d = torch.from_numpy(row_ptr).to(dev, non_blocking=True)
+            ix_d = torch.from_numpy(idx if len(idx) else np.zeros(1, np.int32)).to(dev, non_blocking=True)
+            if targets is None:
+                tp_d, tg_d = rp_d, ix_d
+            else:
+                tp_d = torch.from_numpy(tgt_ptr).to(dev, non_blocking=True)
+                tg_d = torch.from_numpy(tgt if len(tgt) else np.zeros(1, np.int32)).to(dev, non_blocking=True)
+            loss = torch.empty(Rc, device=dev, dtype=torch.float64)
+            pred = torch.empty(Rc, device=dev, dtype=torch.int32)
+            L.call('cc_recommend_batch_loss_fp32', L.ptr(self.params), V, d, Rc, L.ptr(rp_d), L.ptr(ix_d), max_n,
+                   L.ptr(tp_d), L.ptr(tg_d), L.ptr(self._batch_ws), L.ptr(loss), L.ptr(pred),
+                   L.stream_ptr(self.stream))
+            host = [torch.empty(t.shape, dtype=t.dtype, pin_memory=True).copy_(t, non_blocking=True)
+                    for t in (loss, pred)]
+            done = torch.cuda.Event()
+            done.record(self.stream)
+            return r0, r1, host, done
+
+        def collect(r0, r1, host, done):
+            done.synchronize()
+            row_loss[r0:r1] = host[0].numpy()
+            row_pred[r0:r1] = host[1].numpy()
+
+        with self.lock, torch.cuda.stream(self.stream):
+            pending = None      # a launch's results are unpacked while the next one runs
+            for r0 in range(0, R, rows_per_launch):
+                queued = launch(r0, min(R, r0 + rows_per_launch))
+                if pending is not None:
+                    collect(*pending)
+                pending = queued
+            collect(*pending)
+        return row_loss, row_pred
+
     def _full_order(self, probs, uniq, amount):
         """The complete ranking (cc_topn with `order`; tests and tools only)."""
         V, dev = self.V, self.dev

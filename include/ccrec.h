@@ -772,6 +772,28 @@ int cc_recommend_batch_target_ranks_fp32(
     const int32_t *cutoffs, int32_t n_cutoffs, void *ws, int32_t *ranks, float *tgt_vals,
     unsigned long long *hits, float *cut_vals, float *probs, void *stream);
 
+/* Validation loss: the reconstruction output's binary cross-entropy and Keras' categorical-
+ * accuracy prediction of R rows, on the logits of cc_recommend_batch_fp32 (the same batched fp32
+ * forward and output-layer tile), reduced per row on the device: nothing of size R x V is written.
+ *   row_ptr, idx, max_n: the inputs x as for cc_recommend_batch_fp32 (sorted distinct ids in [0, V)).
+ *   tgt_ptr [R + 1], tgt: CSR of the targets y (device); any order, duplicates allowed; ids outside
+ *   [0, V) are ignored (never used as an index).
+ *   row_loss [R] f64: mean over the V cards of max(z, 0) - z*y + log(1 + exp(-|z|)), the terms in
+ *   fp64 from the fp32 logit z with the deterministic exp / log of detmath.hpp, summed in a fixed
+ *   order (4 cards per lane, an xor butterfly over the 16 lanes of a 64-card tile, tiles ascending),
+ *   so equal inputs give equal bits whatever R and whatever else is in the batch.
+ *   row_pred [R] i32: the first index of the maximum of p' = z >= 15.7243833541870117f ? 1 :
+ *   float(1 / (1 + exp(-z))) over the row's V cards (cc_sigmoid_cat_accuracy's rule with the
+ *   deterministic sigmoid).
+ *   ws: cc_recommend_batch_loss_ws_size(V, d, R, max_n) bytes, 256-B aligned; the call does not
+ *   depend on its contents.  R == 0 returns CC_OK without a launch.
+ * CC_ERR_ARG: null pointer, R < 0, max_n > V, d not a multiple of 64 in [64, 1024], unaligned ws. */
+size_t cc_recommend_batch_loss_ws_size(int32_t V, int32_t d, int32_t R, int32_t max_n);
+int cc_recommend_batch_loss_fp32(const float *params, int32_t V, int32_t d, int32_t R,
+                                 const int32_t *row_ptr, const int32_t *idx, int32_t max_n,
+                                 const int32_t *tgt_ptr, const int32_t *tgt, void *ws,
+                                 double *row_loss, int32_t *row_pred, void *stream);
+
 /* ---------------------------------------------------------------- card co-occurrence graph (N1)
  * Replaces src/non_ml/utils.py:75-91 (create_adjacency_matrix, called by
  * src/non_ml/create_mtx.py:19) and the M~ normalisation of src/ml/train.py:69-71.

@@ -4,7 +4,9 @@
 Loads ml_files/<name> with load_model and the cubes the way scripts/train.py does
 (data/maps/nameToId.json + data/cube/*.json, or --synthetic C V with the same seed argument), hides
 --hide of every cube's cards, ranks the hidden ones on the GPU and prints one JSON line:
-recall@K, ndcg@K, hit_rate@K for each K, mrr, n_cubes, n_targets, hits (the device's counters)."""
+recall@K, ndcg@K, hit_rate@K for each K, mrr, n_cubes, n_targets, hits (the device's counters).
+--loss adds bce and output_1_accuracy of the whole, clean cubes (the reconstruction output's loss
+and categorical accuracy, as CC_Recommender.evaluate reports them)."""
 import argparse
 import json
 import os
@@ -19,12 +21,13 @@ def main(argv=None):
     ap.add_argument('ks', nargs='*', type=int, default=[10, 50, 100])
     ap.add_argument('--hide', type=float, default=0.2, help='fraction below 1, or a count')
     ap.add_argument('--seed', type=int, default=0)
+    ap.add_argument('--loss', action='store_true', help='also report bce and output_1_accuracy')
     ap.add_argument('--synthetic', nargs=2, type=int, metavar=('C', 'V'))
     ap.add_argument('--data-dir', default='./data')
     ap.add_argument('--out-dir', default='./ml_files')
     a = ap.parse_args(argv)
     from cubecobrarecommender_amd import data as D
-    from cubecobrarecommender_amd.evaluate import evaluate_holdout
+    from cubecobrarecommender_amd.evaluate import evaluate_holdout, evaluate_loss
     from cubecobrarecommender_amd.model import load_model
     from cubecobrarecommender_amd.synthetic import synthetic_cubes
     model = load_model(os.path.join(a.out_dir, a.name))
@@ -40,6 +43,9 @@ def main(argv=None):
     hide = int(a.hide) if a.hide >= 1 else a.hide
     out = evaluate_holdout(model, cubes, ks=a.ks or [10, 50, 100], hide=hide, seed=a.seed)
     out = {'name': a.name, 'cubes': len(cubes), 'hide': hide, 'seed': a.seed, **out}
+    if a.loss:
+        e = evaluate_loss(model, cubes)
+        out.update({'bce': e['bce'], 'output_1_accuracy': e['output_1_accuracy']})
     print(json.dumps(out))
     return out
 
