@@ -70,6 +70,52 @@ def recommend_many(model, cubes_indices, amount, int_to_card):
     return result
 
 
+def _graph_of(adj_mtx):
+    """adj_mtx as a GraphRecommender: one passed in is used as it is (its graph stays resident);
+    a matrix is uploaded for this call."""
+    if hasattr(adj_mtx, 'recommend_many'):
+        return adj_mtx
+    from . import graphrec
+    return graphrec.GraphRecommender(adj_mtx)
+
+
+def _cube_cards(cube):
+    return np.where(np.asarray(cube) == 1)[0]
+
+
+def simple_recs(cube, adj_mtx, int_to_card=None):
+    """src/scripts/recommend.py:7-18: dense 0/1 cube vector in, every missing card out, best
+    first (ids, or names with int_to_card).  adj_mtx is the f64 graph or a GraphRecommender; the
+    scores are summed on the GPU (cc_graph_rec_f64), the complete order is the host's
+    argsort(kind='stable')[::-1] of them: descending, equal scores higher index first."""
+    cube = np.asarray(cube)
+    scores = _graph_of(adj_mtx).recommend_many([_cube_cards(cube)], 1, want_scores=True)[0]['scores']
+    missing = np.where(cube == 0)[0]
+    rec_ids = [int(i) for i in missing[np.argsort(scores[missing], kind='stable')[::-1]]]
+    return rec_ids if int_to_card is None else [int_to_card[i] for i in rec_ids]
+
+
+def simple_cuts(cube, adj_mtx, int_to_card=None):
+    """src/scripts/cut_cards.py:7-18: dense 0/1 cube vector in, the cube's cards out, first cut
+    first (ascending score, equal scores lower index first).  Unlike the reference this does not
+    zero the caller's diagonal: the kernel never reads it as a value."""
+    rec_ids = [int(i) for i in _graph_of(adj_mtx).recommend_many([_cube_cards(cube)], 1)[0]['cuts']]
+    return rec_ids if int_to_card is None else [int_to_card[i] for i in rec_ids]
+
+
+def graph_recommend(rec, cube_indices, amount, int_to_card):
+    """The co-occurrence baseline in `recommend`'s JSON shape: {"additions": {name: score},
+    "cuts": {name: score}} from GraphRecommender `rec`, the additions best first (`amount` of
+    them), the cuts first cut first (every distinct cube card)."""
+    out = rec.recommend_many([list(cube_indices)], amount)[0]
+    output = {'additions': {}, 'cuts': {}}
+    for idx, s in zip(out['additions'].tolist(), out['add_vals'].tolist()):
+        output['additions'][int_to_card[idx]] = s
+    for idx, s in zip(out['cuts'].tolist(), out['cut_vals'].tolist()):
+        output['cuts'][int_to_card[idx]] = s
+    return output
+
+
 def recommend(model, cube_indices, amount, int_to_card, non_json=False, print_fn=print, print_cuts=True):
     """ml_recommend.py:78-116 / ml_recommend_web.py:39-67 on the GPU.  Returns
     {"additions": {name: p}, "cuts": {name: p}} (additions empty in non_json mode, as the reference

@@ -1,0 +1,205 @@
+"""The co-occurrence baseline on the GPU: additions, cuts and held-out ranks from the card graph.
+
+Replaces ``simple_recs`` (src/scripts/recommend.py:7-18) and ``simple_cuts``
+(src/scripts/cut_cards.py:7-18): score every card by the sum of the co-occurrence rows of the
+cube's cards, recommend the highest-scoring missing cards and cut the lowest-scoring cube cards.
+The graph M (the f64 ``output/full_adj_mtx.npy``, or the matrix ``cc_adjacency`` left on the device)
+stays resident in HBM; cc_graph_rec_f64 (csrc/graphrec.hip) gathers and sums the rows in a pinned
+order and ranks on the device.  The pinned order is ``M[S].sum(axis=0)`` of a C-contiguous M with
+the cube's own diagonal entries taken as 0; the reference's ``adj[contains][:, missing].sum(0)``
+sums the same numbers pairwise and differs in the last bits.
+"""
+import threading
+
+import numpy as np
+import torch
+
+from . import _lib as L
+from .recommender import check_card_ids, pack_cubes, pack_targets
+
+
+class GraphRecommender:
+    def __init__(self, adj, device='cuda'):
+        """adj: the graph, an f64 numpy [V, V] (uploaded once) or an f64 device tensor [V, V] whose
+        rows are contiguous (used in place: a row pitch above V is fine)."""
+        L.lib()
+        if torch.is_tensor(adj):
+            self.dev = adj.device
+            self.adj = adj
+        else:
+            self.dev = torch.device(device)
+            a = np.asarray(adj)
+            if a.dtype != np.float64:
+                raise ValueError('the adjacency matrix must be float64')
+            self.adj = torch.from_numpy(np.ascontiguousarray(a)).to(self.dev)
+        a = self.adj
+        if a.dtype != torch.float64 or a.dim() != 2 or a.shape[0] != a.shape[1] or a.shape[0] < 1:
+            raise ValueError('the adjacency matrix must be a square float64 matrix')
+        if a.shape[1] > 1 and a.stride(1) != 1 or a.shape[0] > 1 and a.stride(0) < a.shape[1]:
+            raise ValueError('the rows of the adjacency matrix must be contiguous')
+        self.V = int(a.shape[0])
+        self.ld = int(a.stride(0)) if self.V > 1 else self.V
+        self.stream = torch.cuda.Stream(device=self.dev)
+        self.lock = threading.Lock()
+        self._ws = None
+        # requests run on the recommender's own stream: the matrix (an upload, or cc_adjacency on
+        # another stream) must be complete before they can
+        torch.cuda.synchronize(self.dev)
+
+    @classmethod
+    def from_cubes(cls, indptr, indices, V, device='cuda'):
+        """The graph of CSR cube lists, built on the device (adjacency.py: cc_adjacency's M)."""
+        from .adjacency import adjacency_gpu
+        return cls(adjacency_gpu(indptr, indices, V, ('M',), device=device)['M'])
+
+    def _workspace(self, Rc, max_n):
+        need = int(L.lib().cc_graph_rec_ws_size(self.V, Rc, max_n)) // 4 + 64
+        if self._ws is None or self._ws.numel() < need:
+            self._ws = torch.empty(need, device=self.dev, dtype=torch.int32)   # grown when needed, kept
+        return self._ws
+
+    # ------------------------------------------------------------------ additions and cuts
+    def recommend(self, cube_indices, amount, want_scores=False):
+        """`recommend_many` for one cube."""
+        return self.recommend_many([cube_indices], amount, want_scores=want_scores)[0]
+
+    def recommend_many(self, cubes, amount, want_scores=False, rows_per_launch=512):
+        """simple_recs and simple_cuts for every cube of `cubes` (card-index lists; duplicates
+        collapse, as in the reference's 0/1 cube vector), in launches of up to rows_per_launch
+        rows.  Returns a list of dicts:
+
+          additions int32, add_vals f64   the min(max(amount, 1), V - n) highest-scoring cards
+                                          outside the cube, descending, equal scores higher index
+                                          first (argsort(kind='stable')[::-1]), and their scores
+          cuts int32, cut_vals f64        the cube's distinct cards in cut order: ascending score,
+                                          equal scores lower index first, and their scores
+          scores f64 [V]                  on request: every card's score
+
+        A row's bits do not depend on the batch or the launch it falls into.  An id outside
+        [0, V) or an amount above cc_graph_rec_max_amount() raises ValueError before anything is
+        launched (the graph path does not rank every card: target_ranks serves evaluation)."""
+        amount = int(amount)
+        rows_per_launch = max(1, int(rows_per_launch))
+        inputs = [np.asarray(c, np.int64).reshape(-1) for c in cubes]
+        R = len(inputs)
+        V, dev = self.V, getattr(self, 'dev', None)
+        check_card_ids(inputs, V)
+        cap = int(L.lib().cc_graph_rec_max_amount())
+        if amount > cap:
+            raise ValueError(f'amount {amount} above the graph path\'s limit of {cap}')
+        if R == 0:
+            return []
+        A = max(amount, 1)
+        out = []
+
+        def launch(r0, r1):
+            """Pack rows r0..r1, queue their launch and the copies of its results to pinned
+            memory; no waiting."""
+            row_ptr, idx, max_n, _, _ = pack_cubes(inputs[r0:r1], V)
+            Rc, nnz = r1 - r0, len(idx)
+            ws = self._workspace(Rc, max_n)
+            rp_d = torch.from_numpy(row_ptr).to(dev, non_blocking=True)
+            ix_d = torch.from_numpy(idx if nnz else np.zeros(1, np.int32)).to(dev, non_blocking=True)
+            ints = torch.empty(Rc * (1 + A), device=dev, dtype=torch.int32)            # n_add, additions
+            flts = torch.empty(Rc * A + max(nnz, 1), device=dev, dtype=torch.float64)  # add_vals, cut_vals
+            scores = torch.empty(Rc, V, device=dev, dtype=torch.float64) if want_scores else None
+            L.call('cc_graph_rec_f64', L.ptr(self.adj), self.ld, V, Rc, L.ptr(rp_d), L.ptr(ix_d), max_n,
+                   amount, L.ptr(ws), L.ptr(ints), L.ptr(ints[Rc:]), L.ptr(flts), L.ptr(flts[Rc * A:]),
+                   L.ptr(scores), L.stream_ptr(self.stream))
+            host = [torch.empty(t.shape, dtype=t.dtype, pin_memory=True).copy_(t, non_blocking=True)
+                    for t in ((ints, flts, scores) if want_scores else (ints, flts))]
+            done = torch.cuda.Event()
+            done.record(self.stream)
+            return r0, r1, row_ptr, idx, host, done
+
+        def collect(r0, r1, row_ptr, idx, host, done):
+            done.synchronize()
+            Rc = r1 - r0
+            ints, flts = host[0].numpy().copy(), host[1].numpy().copy()   # out of the pinned staging
+            nadd, adds, addv = ints[:Rc].tolist(), ints[Rc:].reshape(Rc, A), flts[:Rc * A].reshape(Rc, A)
+            cutv = flts[Rc * A:]
+            for r in range(Rc):
+                k = nadd[r]
+                ids, vals = idx[row_ptr[r]:row_ptr[r + 1]], cutv[row_ptr[r]:row_ptr[r + 1]]
+                order = np.argsort(vals, kind='stable')     # about 360 values: the host's job
+                o = {'additions': adds[r, :k], 'add_vals': addv[r, :k], 'cuts': ids[order], 'cut_vals': vals[order]}
+                if want_scores:
+                    o['scores'] = host[2][r].numpy().copy()
+                out.append(o)
+
+        with self.lock, torch.cuda.stream(self.stream):
+            pending = None      # a launch's results are unpacked while the next one runs
+            for r0 in range(0, R, rows_per_launch):
+                queued = launch(r0, min(R, r0 + rows_per_launch))
+                if pending is not None:
+                    collect(*pending)
+                pending = queued
+            collect(*pending)
+        return out
+
+    # ------------------------------------------------------------------ held-out evaluation
+    def target_ranks(self, cubes, targets, cutoffs=(), rows_per_launch=512):
+        """Where the cards of targets[r] land in the full ranking of cube r's additions, without
+        ranking anything (cc_graph_rec_target_ranks_f64: the scoring pass, then a count per
+        target).  Arguments and return shape of Recommender.target_ranks, so
+        evaluate.evaluate_holdout takes a GraphRecommender as its model: (ranks, vals, hits) with
+        int32 ranks and float64 scores per cube in the caller's target order, hits None without
+        cutoffs, else the device's uint64 counters [len(cutoffs) + 2]."""
+        rows_per_launch = max(1, int(rows_per_launch))
+        cutoffs = [int(k) for k in cutoffs]
+        if len(cutoffs) > 8:
+            raise ValueError('at most 8 cutoffs')
+        inputs = [np.asarray(c, np.int64).reshape(-1) for c in cubes]
+        R = len(inputs)
+        V, dev = self.V, getattr(self, 'dev', None)
+        check_card_ids(inputs, V)
+        tgt_ptr, tgt = pack_targets(targets, inputs, V)
+        nk = len(cutoffs)
+        if R == 0:
+            return [], [], (np.zeros(nk + 2, np.uint64) if nk else None)
+        ranks, vals = [], []
+
+        def launch(r0, r1):
+            row_ptr, idx, max_n, _, _ = pack_cubes(inputs[r0:r1], V)
+            Rc, nnz = r1 - r0, len(idx)
+            t0, t1 = int(tgt_ptr[r0]), int(tgt_ptr[r1])
+            tp = tgt_ptr[r0:r1 + 1] - tgt_ptr[r0]
+            nt = t1 - t0
+            ws = self._workspace(Rc, max_n)
+            rp_d = torch.from_numpy(row_ptr).to(dev, non_blocking=True)
+            ix_d = torch.from_numpy(idx if nnz else np.zeros(1, np.int32)).to(dev, non_blocking=True)
+            tp_d = torch.from_numpy(tp).to(dev, non_blocking=True)
+            tg_d = torch.from_numpy(tgt[t0:t1] if nt else np.zeros(1, np.int32)).to(dev, non_blocking=True)
+            rk = torch.empty(max(nt, 1), device=dev, dtype=torch.int32)
+            tv = torch.empty(max(nt, 1), device=dev, dtype=torch.float64)
+            cuts = torch.empty(max(nnz, 1), device=dev, dtype=torch.float64)   # the chain's; not returned
+            L.call('cc_graph_rec_target_ranks_f64', L.ptr(self.adj), self.ld, V, Rc, L.ptr(rp_d), L.ptr(ix_d),
+                   max_n, L.ptr(tp_d), L.ptr(tg_d), L.ptr(cut_d), nk, L.ptr(ws), L.ptr(rk), L.ptr(tv),
+                   L.ptr(hits_d), L.ptr(cuts), None, L.stream_ptr(self.stream))
+            host = [torch.empty(t.shape, dtype=t.dtype, pin_memory=True).copy_(t, non_blocking=True)
+                    for t in (rk, tv)]
+            done = torch.cuda.Event()
+            done.record(self.stream)
+            return r0, r1, host, done
+
+        def collect(r0, r1, host, done):
+            done.synchronize()
+            rk, tv = host[0].numpy(), host[1].numpy()
+            base = int(tgt_ptr[r0])
+            for r in range(r0, r1):
+                lo, hi = int(tgt_ptr[r]) - base, int(tgt_ptr[r + 1]) - base
+                ranks.append(rk[lo:hi].copy())
+                vals.append(tv[lo:hi].copy())
+
+        with self.lock, torch.cuda.stream(self.stream):
+            cut_d = torch.tensor(cutoffs, device=dev, dtype=torch.int32) if nk else None
+            hits_d = torch.zeros(nk + 2, device=dev, dtype=torch.int64) if nk else None
+            pending = None      # a launch's results are unpacked while the next one runs
+            for r0 in range(0, R, rows_per_launch):
+                queued = launch(r0, min(R, r0 + rows_per_launch))
+                if pending is not None:
+                    collect(*pending)
+                pending = queued
+            collect(*pending)
+            hits = hits_d.cpu().numpy().view(np.uint64) if nk else None
+        return ranks, vals, hits

@@ -812,6 +812,53 @@ int cc_adjacency(const int32_t *row_ptr, const int32_t *idx, int32_t C, int32_t 
                  int32_t chunk_cubes, const double *force_diag, void *ws, int32_t *counts,
                  double *adj, float *adj_norm, void *stream);
 
+/* ---------------------------------------------------------------- co-occurrence baseline (N5)
+ * Replaces simple_recs (src/scripts/recommend.py:7-18) and simple_cuts
+ * (src/scripts/cut_cards.py:7-18) for R cubes per call, on the f64 graph cc_adjacency writes.
+ *   adj: any finite f64 matrix [V][ld], row-major, ld >= V (device).  row_ptr [R + 1], idx,
+ *   max_n: the cubes' CSR with the PRECONDITIONS of cc_recommend_batch_fp32 (ids sorted
+ *   ascending and unique within a row, all in [0, V); the caller validates).
+ *   PINNED ARITHMETIC, for row r with cube S and every card j:
+ *     score_r[j] = fold over i in S ascending of acc = acc + (i == j ? +0.0 : adj[i][j]),
+ *                  acc starting at +0.0
+ *   in f64, every add rounded, no reassociation: simple_recs' column sum for j outside S,
+ *   simple_cuts' (diagonal zeroed) for j in S.  adj's diagonal is never used as a value; n = 0
+ *   gives +0.0 everywhere.  Rankings compare scores as numbers (-0.0 equals +0.0).
+ *   amount <= cc_graph_rec_max_amount() (at least 1024); want_r = min(max(amount, 1), V - n_r);
+ *   A = max(amount, 1).  n_add [R] = want_r; additions / add_vals [R][A]: the cards outside S in
+ *   descending score, equal scores higher index first (argsort(kind='stable')[::-1]), and their
+ *   scores; the unused tail -1 / 0.  cut_vals [row_ptr[R]], aligned with idx: the cube cards'
+ *   scores (the caller orders the cuts: ascending, stable).  scores [R][V] or NULL.
+ *   ws: cc_graph_rec_ws_size(V, R, max_n) bytes, 256-B aligned; the call does not depend on its
+ *   contents.  R == 0 returns CC_OK without a launch.  A row's bits do not depend on R or on
+ *   what else is in the batch.
+ * CC_ERR_ARG: null pointer, ld < V, max_n > V, amount above the limit, unaligned adj or ws.
+ *
+ * cc_graph_rec_target_ranks_f64: the contract of cc_recommend_batch_target_ranks_fp32 on these
+ * scores.  tgt_ptr [R + 1], tgt: CSR of the rows' target cards (device); any order, duplicates
+ * allowed, any number per row.  Target t of row r gets
+ *     ranks    = #{ c outside S : (score_c, c) > (score_t, t) }, t's 0-based position in the
+ *                full ranking of the additions; duplicates get the same rank;
+ *     tgt_vals = score_r[t] (f64).
+ *   A target outside [0, V) or inside the row's cube is invalid: ranks = -1, tgt_vals = 0, counted
+ *   nowhere (and never used as an index).  cutoffs: device array of n_cutoffs (0..8) K values,
+ *   NULL when n_cutoffs == 0.  hits [n_cutoffs + 2] or NULL, zeroed by the caller; the call ADDS,
+ *   per valid target, hits[k] += rank < cutoffs[k] and hits[n_cutoffs] += 1, and
+ *   hits[n_cutoffs + 1] += 1 per row whose best valid target has rank < cutoffs[0] (never with
+ *   n_cutoffs == 0); integer atomics.  cut_vals, scores, ws as above.
+ * CC_ERR_ARG: as above, and n_cutoffs outside 0..8. */
+int32_t cc_graph_rec_max_amount(void);
+size_t cc_graph_rec_ws_size(int32_t V, int32_t R, int32_t max_n);
+int cc_graph_rec_f64(const double *adj, int64_t ld, int32_t V, int32_t R, const int32_t *row_ptr,
+                     const int32_t *idx, int32_t max_n, int32_t amount, void *ws, int32_t *n_add,
+                     int32_t *additions, double *add_vals, double *cut_vals, double *scores,
+                     void *stream);
+int cc_graph_rec_target_ranks_f64(
+    const double *adj, int64_t ld, int32_t V, int32_t R, const int32_t *row_ptr, const int32_t *idx,
+    int32_t max_n, const int32_t *tgt_ptr, const int32_t *tgt, const int32_t *cutoffs,
+    int32_t n_cutoffs, void *ws, int32_t *ranks, double *tgt_vals, unsigned long long *hits,
+    double *cut_vals, double *scores, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

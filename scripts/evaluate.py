@@ -6,7 +6,10 @@ Loads ml_files/<name> with load_model and the cubes the way scripts/train.py doe
 --hide of every cube's cards, ranks the hidden ones on the GPU and prints one JSON line:
 recall@K, ndcg@K, hit_rate@K for each K, mrr, n_cubes, n_targets, hits (the device's counters).
 --loss adds bce and output_1_accuracy of the whole, clean cubes (the reconstruction output's loss
-and categorical accuracy, as CC_Recommender.evaluate reports them)."""
+and categorical accuracy, as CC_Recommender.evaluate reports them).
+--baseline adds "cooccurrence": the same metrics on the same split for the co-occurrence baseline
+(GraphRecommender), its graph built on the GPU from the visible parts of the cubes only: no hidden
+card leaks into it."""
 import argparse
 import json
 import os
@@ -22,12 +25,14 @@ def main(argv=None):
     ap.add_argument('--hide', type=float, default=0.2, help='fraction below 1, or a count')
     ap.add_argument('--seed', type=int, default=0)
     ap.add_argument('--loss', action='store_true', help='also report bce and output_1_accuracy')
+    ap.add_argument('--baseline', action='store_true', help='also report the co-occurrence baseline')
     ap.add_argument('--synthetic', nargs=2, type=int, metavar=('C', 'V'))
     ap.add_argument('--data-dir', default='./data')
     ap.add_argument('--out-dir', default='./ml_files')
     a = ap.parse_args(argv)
     from cubecobrarecommender_amd import data as D
-    from cubecobrarecommender_amd.evaluate import evaluate_holdout, evaluate_loss
+    from cubecobrarecommender_amd import graphrec
+    from cubecobrarecommender_amd.evaluate import evaluate_holdout, evaluate_loss, holdout_split
     from cubecobrarecommender_amd.model import load_model
     from cubecobrarecommender_amd.synthetic import synthetic_cubes
     model = load_model(os.path.join(a.out_dir, a.name))
@@ -46,6 +51,10 @@ def main(argv=None):
     if a.loss:
         e = evaluate_loss(model, cubes)
         out.update({'bce': e['bce'], 'output_1_accuracy': e['output_1_accuracy']})
+    if a.baseline:
+        visible, _ = holdout_split(cubes, hide=hide, seed=a.seed)      # evaluate_holdout's own split
+        graph = graphrec.GraphRecommender.from_cubes(*D.lists_to_csr(visible), V)
+        out['cooccurrence'] = evaluate_holdout(graph, cubes, ks=a.ks or [10, 50, 100], hide=hide, seed=a.seed)
     print(json.dumps(out))
     return out
 
