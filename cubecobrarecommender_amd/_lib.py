@@ -171,6 +171,10 @@ SIGNATURES = {
     'cc_infer_decode_fp32': (C.c_int, [_P, _I32, _I32, _I32, _P, _P, _P, _P]),
     'cc_similar_ws_size': (_SZ, [_I32]),
     'cc_similar_cards': (C.c_int, [_P, _I32, _I32, _I32, _I32, _P, _P, _P, _P, _P]),
+    'cc_similar_batch_max_n': (_I32, []),
+    'cc_similar_batch_ws_size': (_SZ, [_I32, _I32, _I32, _I32]),
+    'cc_similar_cards_batch': (C.c_int, [_P, _I32, _I32, _I32, _P, _I32, _P, _P, _P, _P, _P]),
+    'cc_similar_cards_batch_timed': (C.c_int, [_P, _I32, _I32, _I32, _P, _I32, _P, _P, _P, _P, _P, _P]),
     'cc_embed_grad_packed': (C.c_int, [_P, _I32, _I32, _I32, _I32, _P, _P, _P, _P]),
     **{w1_grad_name(*form): (C.c_int, _w1_grad_args(*form)) for form in W1_GRAD_FORMS},
     'cc_embed_grad_cs_tickets': (_I32, [_I32, _I32, _I32]),

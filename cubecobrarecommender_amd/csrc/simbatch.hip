@@ -1,0 +1,597 @@
+// cc_similar_cards_batch — Q query cards per call, every row bit-identical to cc_similar_cards on
+// it (similarity.hip: the pinned arithmetic, fp32, multiply and add separately rounded, sums in
+// index order).
+//
+// The single-request kernel recomputes both norms for every (query, card) and walks rows at a
+// stride of K floats.  n_j[i] = e_j[i] * inv_j is the very factor it multiplies (qe[i]*invq is
+// n_q[i] of row q), so normalising every card once changes no bit:
+//   normalise_kernel : one thread per card over a tile of 128 rows staged through LDS (pitch 33:
+//                      coalesced loads, conflict-free row walks).  ss_j in index order,
+//                      inv_j = 1/sqrt(max(ss_j, 1e-12)), then n [V][Kp] (row-major, for the
+//                      queries) and nT [Kp][Vs] (k-major, for the cards); Kp = K rounded up to the
+//                      distance kernel's k stage, the pad written as zeros.
+//   dist_tile_kernel : one workgroup per tile of 16*RM queries x 64 cards (recbatch.hip's
+//                      out_tile_kernel with n for both operands).  32 k of nT [32 k][64 cards] and
+//                      of the queries' rows [queries][32 k] are staged in LDS at a time, so any
+//                      K > 0 fits; a thread owns RM queries x 4 cards, one accumulator each:
+//                      dot = dot + n_q[k]*n_j[k] from +0 in index order.  The pad adds +0 * +0 to
+//                      a sum that is never -0: no bit moves.  Writes the sort key
+//                      orderable(-dot) of every (query, card) and the distances only on request.
+//                      Query ids come from device memory; one outside [0, V) is never an index.
+//   select_rows_kernel: one workgroup per query.  The composite (key << 32 | card) is unique, so
+//                      the N smallest are a radix SELECT of the N-th smallest composite (10-bit
+//                      digits from the top, LDS histograms, prefix scan; stops as soon as the
+//                      composites at or below the chosen bin are N or a few more) and a bitonic
+//                      sort of the survivors in LDS, of which the first N are written: ascending
+//                      composite = ascending distance, equal distances lower card first = numpy
+//                      argsort(kind='stable').
+//   sort_rows_kernel : N above the select's cap: one workgroup per query sorts all V
+//                      (key, card) pairs (stable LSD radix sort from ascending card order, four
+//                      8-bit passes — a distance key differs in all 32 bits — through two
+//                      ping-pong buffers in the workspace) and writes the first N.
+// The returned distance is rebuilt from the key: orderable() is a bijection except that it folds
+// -0 onto +0, and a distance is -dot with dot never -0, so a zero distance is always -0.0f.
+#include <algorithm>
+
+#include "common.hpp"
+
+namespace {
+
+constexpr int KS = 32;        // k per LDS stage of the distance tile
+constexpr int TC = 64;        // cards per distance tile
+constexpr int DNT = 256;      // distance-tile workgroup: 16 card groups x 16 query groups
+constexpr int NR = 128;       // normalise: cards per workgroup, one thread each
+constexpr int SNT = 1024;     // select / sort workgroup
+constexpr int MAX_N = 2048;   // survivors sorted in LDS
+constexpr int MAX_Q = 1 << 22;
+constexpr int SBITS = 8;      // sort digit
+constexpr int SR = 1 << SBITS;
+constexpr int SPASSES = 4;
+
+__device__ __forceinline__ float addf(float a, float b) {
+#pragma clang fp contract(off)
+  return a + b;
+}
+__device__ __forceinline__ float mulf(float a, float b) {
+#pragma clang fp contract(off)
+  return a * b;
+}
+
+// similarity.hip's sort key: ascending key == ascending float, -0 folded into +0
+__device__ __forceinline__ uint32_t orderable(float f) {
+  uint32_t u = __float_as_uint(f == 0.f ? 0.f : f);
+  return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
+}
+// its inverse on distances: the only zero a distance takes is -0.0f
+__device__ __forceinline__ float dist_of_key(uint32_t key) {
+  if (key == 0x80000000u) return __uint_as_float(0x80000000u);
+  return __uint_as_float((key & 0x80000000u) ? (key & 0x7FFFFFFFu) : ~key);
+}
+
+// A 128 x 32 tile of emb into LDS, zeros outside [0, V) x [0, K): a thread's 32 loads are issued
+// together (an address that is always valid, the value dropped afterwards), then stored.
+__device__ __forceinline__ void stage_tile(float (*tile)[KS + 1], const float *__restrict__ emb, int V,
+                                           int K, int r0, int k0) {
+  static_assert(NR % KS == 0, "a thread keeps its column: step u holds rows u * NR / KS + tid / KS");
+  const int c = threadIdx.x % KS, rq = threadIdx.x / KS;
+  const bool col_ok = k0 + c < K;
+  float x[KS];
+#pragma unroll
+  for (int u = 0; u < KS; ++u) {
+    const int r = u * (NR / KS) + rq;
+    const bool ok = col_ok && r0 + r < V;
+    const float v = emb[ok ? (int64_t)(r0 + r) * K + k0 + c : 0];
+    x[u] = ok ? v : 0.f;
+  }
+#pragma unroll
+  for (int u = 0; u < KS; ++u) tile[u * (NR / KS) + rq][c] = x[u];
+}
+
+__global__ __launch_bounds__(NR) void normalise_kernel(const float *__restrict__ emb, int V, int K,
+                                                       int Kp, int Vs, float *__restrict__ n,
+                                                       float *__restrict__ nT) {
+#pragma clang fp contract(off)
+  __shared__ float tile[NR][KS + 1];
+  const int tid = threadIdx.x;
+  const int r0 = blockIdx.x * NR, row = r0 + tid;
+  float ss = 0.f;
+  for (int k0 = 0; k0 < Kp; k0 += KS) {
+    __syncthreads();  // the previous stage's readers are done
+    stage_tile(tile, emb, V, K, r0, k0);
+    __syncthreads();
+    const int kc = min(KS, K - k0);
+    for (int c = 0; c < kc; ++c) {
+      const float x = tile[tid][c];
+      ss = ss + x * x;
+    }
+  }
+  const float inv = 1.f / sqrtf(fmaxf(ss, 1e-12f));
+  for (int k0 = 0; k0 < Kp; k0 += KS) {
+    __syncthreads();
+    stage_tile(tile, emb, V, K, r0, k0);
+    __syncthreads();
+#pragma unroll 8
+    for (int c = 0; c < KS; ++c) {
+      const float v = tile[tid][c] * inv;
+      tile[tid][c] = v;
+      if (row < V) nT[(int64_t)(k0 + c) * Vs + row] = v;
+    }
+    __syncthreads();
+    for (int t = tid; t < NR * KS; t += NR) {
+      const int r = t / KS, c = t % KS;
+      if (r0 + r < V) n[(int64_t)(r0 + r) * Kp + k0 + c] = tile[r][c];
+    }
+  }
+}
+
+template <int RM>
+__global__ __launch_bounds__(DNT) void dist_tile_kernel(const float *__restrict__ n,
+                                                        const float *__restrict__ nT, int V,
+                                                        int Kp, int Vs, int Q,
+                                                        const int32_t *__restrict__ queries,
+                                                        uint32_t *__restrict__ keys,
+                                                        float *__restrict__ dist_all) {
+  constexpr int TR = 16 * RM;
+  constexpr int F4 = KS / 4, RS = DNT / F4;  // float4 per query row, query rows per step
+  __shared__ __attribute__((aligned(16))) float wsm[KS][TC];
+  __shared__ __attribute__((aligned(16))) float hsm[TR][KS];
+  const int tid = threadIdx.x;
+  const int tx = tid & 15, ty = tid >> 4;
+  const int nb = blockIdx.x * TC;  // first card of the tile
+  const int rb = blockIdx.y * TR;  // first query of the tile
+  float acc[RM][4];
+#pragma unroll
+  for (int j = 0; j < RM; ++j)
+#pragma unroll
+    for (int e = 0; e < 4; ++e) acc[j][e] = 0.f;
+  // the rows this thread stages: null for a row past Q or a query id outside [0, V)
+  const float *qrow[TR / RS];
+#pragma unroll
+  for (int i = 0; i < TR / RS; ++i) {
+    const int gr = rb + tid / F4 + RS * i;
+    const int q = gr < Q ? queries[gr] : -1;
+    qrow[i] = (uint32_t)q < (uint32_t)V ? n + (int64_t)q * Kp + 4 * (tid % F4) : nullptr;
+  }
+
+  for (int k0 = 0; k0 < Kp; k0 += KS) {
+    __syncthreads();  // the previous stage's readers are done
+    {
+      const int c = tid & 63, gn = nb + c;
+      const float *Wp = nT + ((int64_t)k0 + (tid >> 6)) * Vs + gn;
+      float w[KS / 4];
+#pragma unroll
+      for (int i = 0; i < KS / 4; ++i) w[i] = gn < V ? Wp[(int64_t)(4 * i) * Vs] : 0.f;
+      float4 h[TR / RS];
+#pragma unroll
+      for (int i = 0; i < TR / RS; ++i)
+        h[i] = qrow[i] ? *reinterpret_cast<const float4 *>(qrow[i] + k0) : make_float4(0.f, 0.f, 0.f, 0.f);
+#pragma unroll
+      for (int i = 0; i < KS / 4; ++i) wsm[4 * i + (tid >> 6)][c] = w[i];
+#pragma unroll
+      for (int i = 0; i < TR / RS; ++i)
+        *reinterpret_cast<float4 *>(&hsm[tid / F4 + RS * i][4 * (tid % F4)]) = h[i];
+    }
+    __syncthreads();
+#pragma unroll 2
+    for (int k4 = 0; k4 < KS / 4; ++k4) {
+      float4 w[4];
+#pragma unroll
+      for (int kk = 0; kk < 4; ++kk) w[kk] = *reinterpret_cast<const float4 *>(&wsm[4 * k4 + kk][4 * tx]);
+#pragma unroll
+      for (int j = 0; j < RM; ++j) {
+        const float4 h = *reinterpret_cast<const float4 *>(&hsm[ty * RM + j][4 * k4]);
+        const float hk[4] = {h.x, h.y, h.z, h.w};
+#pragma unroll
+        for (int kk = 0; kk < 4; ++kk) {
+          acc[j][0] = addf(acc[j][0], mulf(hk[kk], w[kk].x));
+          acc[j][1] = addf(acc[j][1], mulf(hk[kk], w[kk].y));
+          acc[j][2] = addf(acc[j][2], mulf(hk[kk], w[kk].z));
+          acc[j][3] = addf(acc[j][3], mulf(hk[kk], w[kk].w));
+        }
+      }
+    }
+  }
+
+  const int n0 = nb + 4 * tx;
+  if (n0 >= V) return;
+#pragma unroll
+  for (int j = 0; j < RM; ++j) {
+    const int gr = rb + ty * RM + j;
+    if (gr >= Q) continue;
+    const bool ok = (uint32_t)queries[gr] < (uint32_t)V;
+    float dd[4];
+    uint32_t key[4];
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+      dd[e] = ok ? -acc[j][e] : 0.f;
+      key[e] = orderable(dd[e]);
+    }
+    uint32_t *kr = keys + (int64_t)gr * Vs + n0;  // Vs % 4 == 0: 16-B aligned, the pad is ours
+    *reinterpret_cast<uint4 *>(kr) = make_uint4(key[0], key[1], key[2], key[3]);
+    if (dist_all) {
+#pragma unroll
+      for (int e = 0; e < 4; ++e)
+        if (n0 + e < V) dist_all[(int64_t)gr * V + n0 + e] = dd[e];
+    }
+  }
+}
+
+// Inclusive scan of one int per thread over the SNT-thread block; wtot: [SNT/64] LDS scratch.
+__device__ __forceinline__ int block_incl_scan(int v, int *wtot) {
+  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+  int x = v;
+#pragma unroll
+  for (int off = 1; off < 64; off <<= 1) {
+    const int y = __shfl_up(x, off, 64);
+    if (lane >= off) x += y;
+  }
+  if (lane == 63) wtot[w] = x;
+  __syncthreads();
+  int before = 0;
+#pragma unroll
+  for (int i = 0; i < SNT / 64; ++i) before += i < w ? wtot[i] : 0;
+  __syncthreads();
+  return before + x;
+}
+
+// A row whose query id is outside [0, V): -1 / 0.f, nothing read.
+__device__ __forceinline__ void fill_invalid_row(int32_t *oi, float *od, int N) {
+  for (int i = threadIdx.x; i < N; i += SNT) {
+    oi[i] = -1;
+    od[i] = 0.f;
+  }
+}
+
+__global__ __launch_bounds__(SNT) void select_rows_kernel(const uint32_t *__restrict__ keys, int Vs,
+                                                          int V, const int32_t *__restrict__ queries,
+                                                          int N, int32_t *__restrict__ out_idx,
+                                                          float *__restrict__ out_dist) {
+  __shared__ uint32_t hist[1024];
+  __shared__ int wtot[SNT / 64];
+  __shared__ uint64_t s_prefix, s_mask;
+  __shared__ int s_rem, s_done, s_cnt;
+  __shared__ uint64_t sel[MAX_N];
+  const int tid = threadIdx.x;
+  const int r = blockIdx.x;
+  int32_t *oi = out_idx + (int64_t)r * N;
+  float *od = out_dist + (int64_t)r * N;
+  if ((uint32_t)queries[r] >= (uint32_t)V) {  // (block-uniform)
+    fill_invalid_row(oi, od, N);
+    return;
+  }
+  const uint32_t *k = keys + (int64_t)r * Vs;
+  // The select stops as soon as the composites at or below the chosen bin fit `limit`: the sort
+  // then orders a few more than N and the first N are written.  One size step of the bitonic
+  // network is cheaper than one more pass over the row, and distances are dense in the key's top
+  // bits only, so two passes usually do.
+  int PN = 1;
+  while (PN < N) PN <<= 1;
+  const int limit = min(MAX_N, 2 * PN);
+  if (tid == 0) {
+    s_prefix = 0;
+    s_mask = 0;
+    s_rem = N;
+    s_done = 0;
+    s_cnt = 0;
+  }
+  __syncthreads();
+  // composite bits: key in 32..63, card in 0..31; digits from the top, the windows split at bit 32
+  // so that a window holding no bit of any card is skipped
+  for (int pass = 0; pass < 8; ++pass) {
+    const int shift = pass < 3 ? 54 - 10 * pass : pass == 3 ? 32 : pass < 7 ? 22 - 10 * (pass - 4) : 0;
+    const uint32_t dmask = (pass == 3 || pass == 7) ? 3u : 1023u;
+    if (shift < 32 && ((uint32_t)(V - 1) >> shift) == 0u) continue;  // no card has a bit up here
+    if (s_done) break;
+    const uint64_t prefix = s_prefix, mask = s_mask;
+    const int rem = s_rem;
+    hist[tid] = 0u;
+    __syncthreads();
+    for (int j = tid; j < V; j += SNT) {
+      const uint64_t cmp = ((uint64_t)k[j] << 32) | (uint32_t)j;
+      if ((cmp & mask) == prefix) atomicAdd(&hist[(uint32_t)(cmp >> shift) & dmask], 1u);
+    }
+    __syncthreads();
+    // thread t owns bin t: its inclusive scan is the count of matching items in bins <= it
+    const int v = (int)hist[tid];
+    const int le = block_incl_scan(v, wtot), lt = le - v;
+    if (le >= rem && lt < rem) {  // exactly one bin: the one holding the rem-th smallest
+      s_prefix = prefix | ((uint64_t)tid << shift);
+      s_mask = mask | ((uint64_t)dmask << shift);
+      s_rem = rem - lt;
+      s_done = (N - (rem - lt)) + v <= limit;  // everything at or below this bin: N or a few more
+    }
+    __syncthreads();
+  }
+  // the bits outside the mask are below every decided digit or zero in every composite: on the
+  // decided bits, a candidate <=> at or below the prefix; all passes done, exactly N of them
+  const uint64_t T = s_prefix, M = s_mask;
+  for (int j = tid; j < V; j += SNT) {
+    const uint64_t cmp = ((uint64_t)k[j] << 32) | (uint32_t)j;
+    if ((cmp & M) <= T) {
+      const int pos = atomicAdd(&s_cnt, 1);
+      if (pos < limit) sel[pos] = cmp;
+    }
+  }
+  __syncthreads();
+  const int cnt = min(s_cnt, limit);  // (N <= cnt <= limit by the counts; never past sel)
+  int P = PN;
+  while (P < cnt) P <<= 1;
+  for (int i = cnt + tid; i < P; i += SNT) sel[i] = ~0ull;  // above every candidate
+  __syncthreads();
+  for (int size = 2; size <= P; size <<= 1)
+    for (int stride = size >> 1; stride > 0; stride >>= 1) {
+      for (int i = tid; i < P; i += SNT) {
+        const int pr = i ^ stride;
+        if (pr > i) {
+          const bool up = (i & size) == 0;
+          const uint64_t a = sel[i], b = sel[pr];
+          if ((a > b) == up) {
+            sel[i] = b;
+            sel[pr] = a;
+          }
+        }
+      }
+      __syncthreads();
+    }
+  for (int i = tid; i < N; i += SNT) {
+    const uint64_t cmp = sel[i];
+    oi[i] = (int32_t)(uint32_t)cmp;
+    od[i] = dist_of_key((uint32_t)(cmp >> 32));
+  }
+}
+
+// Full ranking of one row (recbatch.hip's rank_rows_kernel with a digit plan for 32-bit keys and
+// the ascending order kept): wave w owns a contiguous slice of the current arrangement; inside a
+// wave the rank is a ballot multisplit, across waves the exclusive scan of the (digit, wave)
+// counts in digit-major order.  (key, card) pairs ping-pong through pa / pb as one 64-bit word;
+// the last pass stores nothing but the row's first N.
+__device__ __forceinline__ uint64_t sort_load(const uint32_t *k, const uint64_t *src, int pass, int i) {
+  return pass == 0 ? ((uint64_t)k[i] << 32) | (uint32_t)i : src[i];
+}
+__device__ __forceinline__ uint32_t sort_digit(uint32_t key, int pass) {
+  return (key >> (SBITS * pass)) & (uint32_t)(SR - 1);
+}
+// the valid lanes of the wave that hold digit dg
+__device__ __forceinline__ uint64_t sort_match(uint32_t dg, bool valid) {
+  uint64_t m = __ballot(valid);
+#pragma unroll
+  for (int bit = 0; bit < SBITS; ++bit) {
+    const bool b = (dg >> bit) & 1u;
+    const uint64_t bb = __ballot(b);
+    m &= b ? bb : ~bb;
+  }
+  return m;
+}
+constexpr int RU = 8;  // items a lane loads ahead of ranking them
+
+__global__ __launch_bounds__(SNT) void sort_rows_kernel(const uint32_t *__restrict__ keys, int Vs,
+                                                        int V, const int32_t *__restrict__ queries,
+                                                        int N, uint64_t *pa, uint64_t *pb, int Vp,
+                                                        int32_t *__restrict__ out_idx,
+                                                        float *__restrict__ out_dist) {
+  constexpr int NW = SNT / 64;
+  static_assert(SPASSES % 2 == 0 && SBITS * SPASSES == 32, "pass 0 reads the keys, the last writes the results");
+  __shared__ uint32_t hist[NW * SR];  // [wave][digit]: a thread scans its digit's column
+  __shared__ int wtot[NW];
+  const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+  const uint64_t lt = (1ull << lane) - 1ull;
+  const int r = blockIdx.x;
+  int32_t *oi = out_idx + (int64_t)r * N;
+  float *od = out_dist + (int64_t)r * N;
+  if ((uint32_t)queries[r] >= (uint32_t)V) {  // (block-uniform)
+    fill_invalid_row(oi, od, N);
+    return;
+  }
+  const uint32_t *k = keys + (int64_t)r * Vs;
+  uint64_t *bufa = pa + (int64_t)r * Vp, *bufb = pb + (int64_t)r * Vp;
+  const int S = (int)cdiv(cdiv(V, NW), 64) * 64;  // per-wave slice
+  const int lo = min(V, w * S), hi = min(V, lo + S);
+  uint32_t *hw = hist + w * SR;
+  for (int pass = 0; pass < SPASSES; ++pass) {
+    const uint64_t *src = (pass & 1) ? bufa : bufb;  // pass 0 reads the keys instead
+    uint64_t *dst = (pass & 1) ? bufb : bufa;
+    const bool last = pass == SPASSES - 1;
+    for (int i = tid; i < NW * SR; i += SNT) hist[i] = 0u;
+    __syncthreads();
+    for (int base0 = lo; base0 < hi; base0 += 64 * RU) {
+      uint64_t item[RU];
+#pragma unroll
+      for (int u = 0; u < RU; ++u) {
+        const int i = base0 + 64 * u + lane;
+        item[u] = i < hi ? sort_load(k, src, pass, i) : 0ull;
+      }
+#pragma unroll
+      for (int u = 0; u < RU; ++u) {
+        if (base0 + 64 * u >= hi) break;
+        const bool valid = base0 + 64 * u + lane < hi;
+        const uint32_t dg = sort_digit((uint32_t)(item[u] >> 32), pass);
+        const uint64_t m = sort_match(dg, valid);
+        if (valid && (m & lt) == 0) hw[dg] += (uint32_t)__popcll(m);
+      }
+    }
+    __syncthreads();
+    {  // exclusive scan in (digit, wave) order; thread tid < SR owns digit tid
+      uint32_t c[NW];
+      int s = 0;
+      if (tid < SR) {
+#pragma unroll
+        for (int i = 0; i < NW; ++i) {
+          c[i] = hist[i * SR + tid];
+          s += (int)c[i];
+        }
+      }
+      int off = block_incl_scan(s, wtot) - s;
+      if (tid < SR) {
+#pragma unroll
+        for (int i = 0; i < NW; ++i) {
+          hist[i * SR + tid] = (uint32_t)off;
+          off += (int)c[i];
+        }
+      }
+    }
+    __syncthreads();
+    for (int base0 = lo; base0 < hi; base0 += 64 * RU) {
+      uint64_t item[RU];
+#pragma unroll
+      for (int u = 0; u < RU; ++u) {
+        const int i = base0 + 64 * u + lane;
+        item[u] = i < hi ? sort_load(k, src, pass, i) : 0ull;
+      }
+#pragma unroll
+      for (int u = 0; u < RU; ++u) {
+        if (base0 + 64 * u >= hi) break;
+        const bool valid = base0 + 64 * u + lane < hi;
+        const uint32_t key = (uint32_t)(item[u] >> 32);
+        const uint32_t dg = sort_digit(key, pass);
+        const uint64_t m = sort_match(dg, valid);
+        const uint32_t basepos = hw[dg];
+        const uint32_t pos = basepos + (uint32_t)__popcll(m & lt);
+        if (valid && pos < (uint32_t)V) {  // pos >= V needs inconsistent counts: never write there
+          if (last) {
+            if (pos < (uint32_t)N) {
+              oi[pos] = (int32_t)(uint32_t)item[u];
+              od[pos] = dist_of_key(key);
+            }
+          } else {
+            dst[pos] = item[u];
+          }
+        }
+        if (valid && (m & lt) == 0) hw[dg] = basepos + (uint32_t)__popcll(m);
+      }
+    }
+    __threadfence_block();
+    __syncthreads();
+  }
+}
+
+inline size_t align256(size_t x) { return (x + 255) & ~(size_t)255; }
+
+// workspace: [n V*Kp][nT Kp*Vs][keys Q*Vs] and, for N above the select's cap, the two
+// (key, card) ping-pong buffers [Q][Vp] of 64-bit words (Vp a multiple of 16: no two rows share a
+// 128-byte line)
+struct SimWs {
+  size_t n, nT, keys, pa, pb, total;
+  int Kp, Vs, Vp;
+};
+SimWs sim_ws(int V, int K, int Q, int N) {
+  SimWs w;
+  const size_t v = (size_t)std::max(V, 1), q = (size_t)std::max(Q, 1);
+  w.Kp = (int)cdiv(std::max(K, 1), KS) * KS;
+  w.Vs = (int)((v + 3) & ~(size_t)3);
+  w.Vp = (int)((v + 15) & ~(size_t)15);
+  size_t o = 0;
+  w.n = o, o += align256(v * w.Kp * sizeof(float));
+  w.nT = o, o += align256((size_t)w.Kp * w.Vs * sizeof(float));
+  w.keys = o, o += align256(q * w.Vs * sizeof(uint32_t));
+  w.pa = w.pb = o;
+  if (N > MAX_N) {
+    w.pa = o, o += align256(q * w.Vp * sizeof(uint64_t));
+    w.pb = o, o += align256(q * w.Vp * sizeof(uint64_t));
+  }
+  w.total = o;
+  return w;
+}
+
+template <int RM>
+void launch_dist(hipStream_t s, const float *n, const float *nT, int V, int Kp, int Vs, int Q,
+                 const int32_t *queries, uint32_t *keys, float *dist_all) {
+  const dim3 grid((unsigned)cdiv(V, TC), (unsigned)cdiv(Q, 16 * RM));
+  hipLaunchKernelGGL(dist_tile_kernel<RM>, grid, dim3(DNT), 0, s, n, nT, V, Kp, Vs, Q, queries, keys,
+                     dist_all);
+}
+
+}  // namespace
+
+extern "C" int32_t cc_similar_batch_max_n(void) { return MAX_N; }
+
+extern "C" size_t cc_similar_batch_ws_size(int32_t V, int32_t K, int32_t Q, int32_t N) {
+  return sim_ws(V, K, Q, N).total + 256;
+}
+
+// Every argument check of both entries, before anything is created or launched.
+static int similar_batch_check(const char *who, const float *emb, int V, int K, int Q,
+                               const int32_t *queries, int N, void *ws, int32_t *out_idx,
+                               float *out_dist) {
+  const std::string name(who);
+  CC_REQUIRE(emb && queries && ws && out_idx && out_dist, name + ": null pointer");
+  CC_REQUIRE(V > 0 && K > 0 && V <= 0x7FFFFFFF - 64 && K <= 0x7FFFFFFF - KS, name + ": bad V/K");
+  CC_REQUIRE(Q >= 0 && Q <= MAX_Q, name + ": Q outside 0..2^22");
+  CC_REQUIRE(N >= 1 && N <= V, name + ": N must be 1..V");
+  CC_REQUIRE(((uintptr_t)ws & 255) == 0, name + ": ws must be 256-byte aligned");
+  return CC_OK;
+}
+
+// The launches of both entries (arguments checked).  ev (the timed entry): four events recorded
+// before the first kernel and behind each of the three.
+static int similar_batch_launch(const float *emb, int V, int K, int Q, const int32_t *queries, int N,
+                                void *ws, int32_t *out_idx, float *out_dist, float *dist_all,
+                                hipStream_t s, hipEvent_t *ev) {
+  if (Q == 0) return CC_OK;
+  const SimWs w = sim_ws(V, K, Q, N);
+  char *base = (char *)ws;
+  float *n = (float *)(base + w.n), *nT = (float *)(base + w.nT);
+  uint32_t *keys = (uint32_t *)(base + w.keys);
+  if (ev) CC_HIP(hipEventRecord(ev[0], s));
+  hipLaunchKernelGGL(normalise_kernel, dim3((unsigned)cdiv(V, NR)), dim3(NR), 0, s, emb, V, K, w.Kp,
+                     w.Vs, n, nT);
+  CC_LAUNCH_CHECK("normalise_kernel");
+  if (ev) CC_HIP(hipEventRecord(ev[1], s));
+  // queries per tile: 32 / 64 / 128 (the arithmetic per (query, card) does not depend on it)
+  if (Q <= 32)
+    launch_dist<2>(s, n, nT, V, w.Kp, w.Vs, Q, queries, keys, dist_all);
+  else if (Q <= 64)
+    launch_dist<4>(s, n, nT, V, w.Kp, w.Vs, Q, queries, keys, dist_all);
+  else
+    launch_dist<8>(s, n, nT, V, w.Kp, w.Vs, Q, queries, keys, dist_all);
+  CC_LAUNCH_CHECK("dist_tile_kernel");
+  if (ev) CC_HIP(hipEventRecord(ev[2], s));
+  if (N <= MAX_N) {
+    hipLaunchKernelGGL(select_rows_kernel, dim3(Q), dim3(SNT), 0, s, keys, w.Vs, V, queries, N,
+                       out_idx, out_dist);
+    CC_LAUNCH_CHECK("select_rows_kernel");
+  } else {
+    hipLaunchKernelGGL(sort_rows_kernel, dim3(Q), dim3(SNT), 0, s, keys, w.Vs, V, queries, N,
+                       (uint64_t *)(base + w.pa), (uint64_t *)(base + w.pb), w.Vp, out_idx, out_dist);
+    CC_LAUNCH_CHECK("sort_rows_kernel");
+  }
+  if (ev) CC_HIP(hipEventRecord(ev[3], s));
+  return CC_OK;
+}
+
+extern "C" int cc_similar_cards_batch(const float *emb, int32_t V, int32_t K, int32_t Q,
+                                      const int32_t *queries, int32_t N, void *ws, int32_t *out_idx,
+                                      float *out_dist, float *dist_all, void *stream) {
+  if (int rc = similar_batch_check("cc_similar_cards_batch", emb, V, K, Q, queries, N, ws, out_idx, out_dist))
+    return rc;
+  return similar_batch_launch(emb, V, K, Q, queries, N, ws, out_idx, out_dist, dist_all,
+                              as_stream(stream), nullptr);
+}
+
+// The same call for measurements (tools/similarity_batch_bench.py): HIP events around each kernel,
+// then a wait for the last one.  kernel_ms: host [3] = normalise, distance tile, select or sort.
+extern "C" int cc_similar_cards_batch_timed(const float *emb, int32_t V, int32_t K, int32_t Q,
+                                            const int32_t *queries, int32_t N, void *ws,
+                                            int32_t *out_idx, float *out_dist, float *dist_all,
+                                            float *kernel_ms, void *stream) {
+  CC_REQUIRE(kernel_ms, "cc_similar_cards_batch_timed: null pointer");
+  int rc = similar_batch_check("cc_similar_cards_batch_timed", emb, V, K, Q, queries, N, ws, out_idx, out_dist);
+  if (rc != CC_OK) return rc;
+  kernel_ms[0] = kernel_ms[1] = kernel_ms[2] = 0.f;
+  if (Q == 0) return CC_OK;
+  hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};
+  for (int i = 0; i < 4 && rc == CC_OK; ++i)
+    if (hipEventCreate(&ev[i]) != hipSuccess) rc = cc::fail(CC_ERR_HIP, "cc_similar_cards_batch_timed: hipEventCreate");
+  if (rc == CC_OK)
+    rc = similar_batch_launch(emb, V, K, Q, queries, N, ws, out_idx, out_dist, dist_all,
+                              as_stream(stream), ev);
+  if (rc == CC_OK) {
+    if (hipEventSynchronize(ev[3]) != hipSuccess)
+      rc = cc::fail(CC_ERR_HIP, "cc_similar_cards_batch_timed: hipEventSynchronize");
+    for (int i = 0; i < 3 && rc == CC_OK; ++i)
+      if (hipEventElapsedTime(&kernel_ms[i], ev[i], ev[i + 1]) != hipSuccess)
+        rc = cc::fail(CC_ERR_HIP, "cc_similar_cards_batch_timed: hipEventElapsedTime");
+  }
+  for (int i = 0; i < 4; ++i)
+    if (ev[i]) (void)hipEventDestroy(ev[i]);
+  return rc;
+}

@@ -2,7 +2,10 @@
 the identity (cc_infer_encode_fp32 on one-card rows, the same kernel as model.encoder) gives the
 [V, 64] card embeddings, cached per model; cc_similar_cards scores every card against the query
 with Keras CosineSimilarity and returns the N smallest distances (argsort order, ties -> lower
-index first)."""
+index first).  similar_many / similarity_table serve many query cards per call
+(cc_similar_cards_batch: every card normalised once, the rows ranked on the device)."""
+import threading
+
 import numpy as np
 import torch
 
@@ -53,3 +56,92 @@ def similar_cards(model, name, N, int_to_card, card_to_int):
     emb = card_embeddings(model)
     idx, dists = similar(emb, card_to_int[name], N)
     return [(i + 1, int_to_card[int(j)], float(dv)) for i, (j, dv) in enumerate(zip(idx, dists))]
+
+
+# ---------------------------------------------------------------------- many query cards per call
+_ws_lock = threading.Lock()
+_ws = {}          # device -> the batched entry's workspace: grown when needed, kept
+
+
+def _workspace(dev, V, K, Q, N):
+    need = int(L.lib().cc_similar_batch_ws_size(V, K, Q, N)) // 4 + 64
+    ws = _ws.get(dev)
+    if ws is None or ws.numel() < need:
+        ws = _ws[dev] = torch.empty(need, device=dev, dtype=torch.int32)
+    return ws
+
+
+def _similar_rows(emb, queries, n, rows_per_launch, idx_dtype):
+    """cc_similar_cards_batch on queries (int32, all inside [0, V)) in launches of up to
+    rows_per_launch rows: (indices idx_dtype [Q, n], dists float32 [Q, n]).  A launch's results
+    are copied to pinned memory behind it and unpacked while the next launch runs."""
+    V, K = emb.shape
+    Q, dev = len(queries), emb.device
+    out_i, out_d = np.empty((Q, n), idx_dtype), np.empty((Q, n), np.float32)
+
+    def launch(r0, r1):
+        Rc = r1 - r0
+        ws = _workspace(dev, V, K, Rc, n)
+        q_d = torch.from_numpy(queries[r0:r1]).to(dev, non_blocking=True)
+        idx = torch.empty(Rc, n, device=dev, dtype=torch.int32)
+        dist = torch.empty(Rc, n, device=dev, dtype=torch.float32)
+        L.call('cc_similar_cards_batch', L.ptr(emb), V, K, Rc, L.ptr(q_d), n, L.ptr(ws), L.ptr(idx),
+               L.ptr(dist), None, L.stream_ptr())
+        host = [torch.empty(t.shape, dtype=t.dtype, pin_memory=True).copy_(t, non_blocking=True)
+                for t in (idx, dist)]
+        done = torch.cuda.Event()
+        done.record()
+        return r0, r1, host, done
+
+    def collect(r0, r1, host, done):
+        done.synchronize()
+        out_i[r0:r1] = host[0].numpy()
+        out_d[r0:r1] = host[1].numpy()
+
+    with _ws_lock:        # one workspace per device: one caller at a time
+        pending = None
+        for r0 in range(0, Q, rows_per_launch):
+            queued = launch(r0, min(Q, r0 + rows_per_launch))
+            if pending is not None:
+                collect(*pending)
+            pending = queued
+        collect(*pending)
+        torch.cuda.current_stream().synchronize()   # the workspace is free for the next caller's stream
+    return out_i, out_d
+
+
+def similar_many(emb, idxs, N, rows_per_launch=512):
+    """`similar` for every card of idxs (duplicates allowed) through cc_similar_cards_batch:
+    (indices int64 [Q, n], dists float32 [Q, n]) with n = min(N, V), every row the bits
+    similar(emb, idx, N) returns, whatever batch or launch it falls into.  N <= 0 gives [Q, 0]
+    arrays; an id outside [0, V) raises ValueError before anything is launched."""
+    V, K = emb.shape
+    q = np.asarray(idxs, np.int64).reshape(-1)
+    bad = np.flatnonzero((q < 0) | (q >= V))
+    if len(bad):
+        raise ValueError(f'query {int(bad[0])}: card id {int(q[bad[0]])} outside [0, {V})')
+    n = max(0, min(int(N), V))
+    if n == 0 or len(q) == 0:
+        return np.zeros((len(q), n), np.int64), np.zeros((len(q), n), np.float32)
+    return _similar_rows(emb.contiguous(), q.astype(np.int32), n, max(1, int(rows_per_launch)), np.int64)
+
+
+def similar_cards_many(model, names, N, int_to_card, card_to_int):
+    """`similar_cards` for every name of names, in one batched request: a list of
+    [(rank, name, dist)] lists."""
+    emb = card_embeddings(model)
+    idx, dists = similar_many(emb, [card_to_int[name] for name in names], N)
+    return [[(i + 1, int_to_card[int(j)], float(dv)) for i, (j, dv) in enumerate(zip(row, drow))]
+            for row, drow in zip(idx, dists)]
+
+
+def similarity_table(model_or_emb, N, rows_per_launch=512):
+    """The N nearest cards of every card: (indices int32 [V, n], dists float32 [V, n]),
+    n = min(N, V); row j is similar(emb, j, N).  Takes a model or its [V, K] embeddings."""
+    emb = model_or_emb if torch.is_tensor(model_or_emb) else card_embeddings(model_or_emb)
+    V = emb.shape[0]
+    n = max(0, min(int(N), V))
+    if n == 0:
+        return np.zeros((V, 0), np.int32), np.zeros((V, 0), np.float32)
+    return _similar_rows(emb.contiguous(), np.arange(V, dtype=np.int32), n, max(1, int(rows_per_launch)),
+                         np.int32)

@@ -671,6 +671,28 @@ size_t cc_similar_ws_size(int32_t V);
 int cc_similar_cards(const float *emb, int32_t V, int32_t K, int32_t q, int32_t N, int32_t *out_idx,
                      float *out_dist, float *dist_all, void *ws, void *stream);
 
+/* Batched card similarity: Q query cards per call (queries: device int32 [Q], duplicates
+ * allowed), every row bit-identical to cc_similar_cards on it.  Every card is normalised once,
+ * one distance tile is shared by many queries, and each query row is ranked on the device: up to
+ * cc_similar_batch_max_n() by a radix select, above it by a full stable sort of the row, chosen
+ * by the entry; any 1 <= N <= V.  out_idx / out_dist [Q][N]: the N smallest by numpy
+ * argsort(kind='stable').  dist_all (optional) [Q][V]: every distance.  A query id outside
+ * [0, V) is never used as an index: its row is -1 / 0.f.  ws: cc_similar_batch_ws_size(V, K, Q, N)
+ * bytes, 256-byte aligned; nothing in it is assumed to survive from an earlier call.  Q == 0
+ * returns CC_OK and launches nothing.
+ * ---------------------------------------------------------------------------------- */
+int32_t cc_similar_batch_max_n(void);
+size_t cc_similar_batch_ws_size(int32_t V, int32_t K, int32_t Q, int32_t N);
+int cc_similar_cards_batch(const float *emb, int32_t V, int32_t K, int32_t Q, const int32_t *queries,
+                           int32_t N, void *ws, int32_t *out_idx, float *out_dist, float *dist_all,
+                           void *stream);
+/* The same call for measurements: HIP events around each of its three kernels, then a wait for the
+ * last one (this entry alone is not stream-ordered).  kernel_ms: host [3] = normalise, distance
+ * tile, select or sort, in milliseconds. */
+int cc_similar_cards_batch_timed(const float *emb, int32_t V, int32_t K, int32_t Q,
+                                 const int32_t *queries, int32_t N, void *ws, int32_t *out_idx,
+                                 float *out_dist, float *dist_all, float *kernel_ms, void *stream);
+
 /* ----------------------------------------------------------------------------------
  * Top-N (ml_recommend.py:87-108): rank all V probabilities descending, ties -> higher
  * index first (= numpy argsort(kind='stable')[::-1]); additions = first max(amount,1)
