@@ -212,6 +212,16 @@ SIGNATURES = {
     'cc_recommend_batch_target_ranks_ws_size': (_SZ, [_I32, _I32, _I32, _I32]),
     'cc_recommend_batch_target_ranks_fp32': (C.c_int, [_P, _I32, _I32, _I32, _P, _P, _I32, _P, _P, _P, _I32, _P,
                                                        _P, _P, _P, _P, _P, _P]),
+    # card pools: the unpooled entry's arguments, then pools, n_pools, pool_of_row before the stream
+    'cc_recommend_batch_pool_ws_size': (_SZ, [_I32, _I32, _I32, _I32]),
+    'cc_recommend_batch_pool_fp32': (C.c_int, [_P, _I32, _I32, _I32, _P, _P, _I32, _I32, _P, _P, _P, _P, _P, _P,
+                                               _P, _I32, _P, _P]),
+    'cc_recommend_batch_rank_pool_ws_size': (_SZ, [_I32, _I32, _I32, _I32]),
+    'cc_recommend_batch_rank_pool_fp32': (C.c_int, [_P, _I32, _I32, _I32, _P, _P, _I32, _I32, _P, _P, _P, _P, _P,
+                                                    _P, _P, _I32, _P, _P]),
+    'cc_recommend_batch_target_ranks_pool_ws_size': (_SZ, [_I32, _I32, _I32, _I32]),
+    'cc_recommend_batch_target_ranks_pool_fp32': (C.c_int, [_P, _I32, _I32, _I32, _P, _P, _I32, _P, _P, _P, _I32,
+                                                            _P, _P, _P, _P, _P, _P, _P, _I32, _P, _P]),
     'cc_recommend_batch_loss_ws_size': (_SZ, [_I32, _I32, _I32, _I32]),
     'cc_recommend_batch_loss_fp32': (C.c_int, [_P, _I32, _I32, _I32, _P, _P, _I32, _P, _P, _P, _P, _P, _P]),
     'cc_adjacency_ws_size': (_SZ, [_I32, _I32, _I32, _I32]),

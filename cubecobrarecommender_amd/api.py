@@ -43,6 +43,24 @@ def cube_indices_of(card_names, card_to_int):
     return out
 
 
+def load_pool(path, card_to_int):
+    """A card pool file, one card name per line -> (ids, n_unknown): the ids of the names the
+    model knows (normalised as cube_indices_of does, in file order, duplicates kept) and the
+    number of non-empty lines it does not.  Pass the ids to Recommender.card_pool."""
+    ids, n_unknown = [], 0
+    with open(path, 'r', encoding='utf8') as fh:
+        for line in fh:
+            name = line.strip()
+            if not name:
+                continue
+            idx = card_to_int.get(normalize(name))
+            if idx is None:
+                n_unknown += 1
+            else:
+                ids.append(idx)
+    return ids, n_unknown
+
+
 def get_model(path):
     """Resident model per checkpoint directory (thread-safe; Flask runs threaded)."""
     from .model import load_model
@@ -52,13 +70,14 @@ def get_model(path):
         return _models[path]
 
 
-def recommend_many(model, cubes_indices, amount, int_to_card):
+def recommend_many(model, cubes_indices, amount, int_to_card, pool=None):
     """`recommend` in JSON mode for many cubes at once (Recommender.recommend_many): a list of
     {"additions": {name: p}, "cuts": {name: p}}, one per cube, equal to the single-cube results.
     Any amount stays on the batched path: above cc_recommend_batch_max_amount() (the web
-    endpoint's default of 30000 ranks every card) each row is sorted on the device."""
+    endpoint's default of 30000 ranks every card) each row is sorted on the device.  pool: a
+    CardPool for every cube, or one (or None) per cube: the additions come from the pool alone."""
     cubes_indices = [list(c) for c in cubes_indices]
-    outs = model.recommender().recommend_many(cubes_indices, amount)
+    outs = model.recommender().recommend_many(cubes_indices, amount, pool=pool)
     result = []
     for cube_indices, out in zip(cubes_indices, outs):
         output = {'additions': {}, 'cuts': {}}
@@ -116,13 +135,15 @@ def graph_recommend(rec, cube_indices, amount, int_to_card):
     return output
 
 
-def recommend(model, cube_indices, amount, int_to_card, non_json=False, print_fn=print, print_cuts=True):
+def recommend(model, cube_indices, amount, int_to_card, non_json=False, print_fn=print, print_cuts=True,
+              pool=None):
     """ml_recommend.py:78-116 / ml_recommend_web.py:39-67 on the GPU.  Returns
     {"additions": {name: p}, "cuts": {name: p}} (additions empty in non_json mode, as the reference
     prints instead of storing them).  print_cuts: in non_json mode also print the lowest-scoring
     cuts — the CLI does (ml_recommend.py:110-116), the web function does not
-    (ml_recommend_web.py:50-67 prints only the additions)."""
-    out = model.recommender().recommend(cube_indices, amount)
+    (ml_recommend_web.py:50-67 prints only the additions).  pool: a CardPool; the additions then
+    come from the pool alone (the cuts are every cube card's, as without one)."""
+    out = model.recommender().recommend(cube_indices, amount, pool=pool)
     output = {'additions': {}, 'cuts': {}}
     for idx, p in zip(out['additions'].tolist(), out['add_vals'].tolist()):
         card = int_to_card[idx]

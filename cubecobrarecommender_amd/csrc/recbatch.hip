@@ -31,6 +31,13 @@
 // cc_recommend_batch_target_ranks_fp32 runs the same chain and then, instead of ranking the row,
 //   target_ranks_kernel: one workgroup per row counts, for each of the row's chosen target cards,
 //                     the candidates ranked before it (held-out evaluation; see the kernel).
+// The *_pool_* entries run the same three chains with a second reason for key' = 0: a row may name
+// a card pool (a bit row of allowed cards), and its candidates are the pool's cards outside the cube.
+//   row_mask_kernel : replaces row_bits_kernel: the row's cube bit row, its exclusion bit row
+//                     (cube | ~pool) and n_cand[r], the cards with the exclusion bit clear.
+//   out_tile_kernel<RM, true> takes the key from the exclusion word and the cut-value search from
+//                     the cube word; topn_rows_kernel<true> / rank_rows_kernel<true> take want from
+//                     n_cand[r] instead of V - n; target_ranks_kernel is fed the pooled keys.
 #include "common.hpp"
 #include "detmath.hpp"
 #include "topn_tiles.hpp"
@@ -77,12 +84,62 @@ __global__ __launch_bounds__(256) void row_bits_kernel(const int32_t *__restrict
   }
 }
 
-template <int RM>
+// The pooled chain's row masks.  pools: [n_pools][VW] bit rows of allowed cards; pool_of_row[r] = -1:
+// the row has no pool (every card allowed); any other value outside [0, n_pools) is never used as
+// an index and allows nothing.  Bits at or above V of a pool row are ignored: the last word's count
+// is masked to its V & 31 valid bits (the exclusion bits up there are never read as a card's).
+// n_cand[r] = allowed cards - the cube cards among them: a cube card's atomicOr on the exclusion
+// row returns the word as it was, so exactly one thread sees its bit go from clear to set.
+// Integer sums: any reduction order gives the same count.  0 <= n_cand[r] <= V - n.
+__global__ __launch_bounds__(256) void row_mask_kernel(const int32_t *__restrict__ row_ptr,
+                                                       const int32_t *__restrict__ idx, int V,
+                                                       int VW, const uint32_t *__restrict__ pools,
+                                                       int n_pools,
+                                                       const int32_t *__restrict__ pool_of_row,
+                                                       uint32_t *__restrict__ bits,
+                                                       uint32_t *__restrict__ excl,
+                                                       int32_t *__restrict__ n_cand) {
+  __shared__ int wsum[256 / 64];
+  const int r = blockIdx.x;
+  uint32_t *b = bits + (int64_t)r * VW;
+  uint32_t *x = excl + (int64_t)r * VW;
+  const int p = pool_of_row[r];
+  const bool has_pool = (uint32_t)p < (uint32_t)n_pools;  // (block-uniform)
+  const uint32_t *pw = has_pool ? pools + (int64_t)p * VW : nullptr;
+  int cnt = 0;
+  for (int i = threadIdx.x; i < VW; i += 256) {
+    uint32_t allowed = has_pool ? pw[i] : (p == -1 ? ~0u : 0u);
+    if (i == VW - 1 && (V & 31)) allowed &= (1u << (V & 31)) - 1u;
+    b[i] = 0u;
+    x[i] = ~allowed;
+    cnt += __popc(allowed);
+  }
+  __syncthreads();
+  const int beg = row_ptr[r], end = row_ptr[r + 1];
+  for (int i = beg + (int)threadIdx.x; i < end; i += 256) {
+    const int j = idx[i];
+    if ((uint32_t)j < (uint32_t)V) {
+      const uint32_t bit = 1u << (j & 31);
+      atomicOr(&b[j >> 5], bit);
+      if (!(atomicOr(&x[j >> 5], bit) & bit)) --cnt;  // an allowed card that the cube takes
+    }
+  }
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) cnt += __shfl_xor(cnt, off);
+  if ((threadIdx.x & 63) == 0) wsum[threadIdx.x >> 6] = cnt;
+  __syncthreads();
+  if (threadIdx.x == 0) n_cand[r] = wsum[0] + wsum[1] + wsum[2] + wsum[3];
+}
+
+// POOL: the key comes from the row's exclusion word (excl: cube | ~pool), the cut-value slot search
+// stays driven by the cube word, so a card that is merely outside the pool never enters the binary
+// search.  Without POOL excl is not read.
+template <int RM, bool POOL>
 __global__ __launch_bounds__(ONT) void out_tile_kernel(
     const float *__restrict__ h3, const float *__restrict__ Wo, const float *__restrict__ bo, int d,
     int V, int R, const int32_t *__restrict__ row_ptr, const int32_t *__restrict__ idx,
     const uint32_t *__restrict__ bits, int VW, uint32_t *__restrict__ keys, int Vs,
-    float *__restrict__ cut_vals, float *__restrict__ probs) {
+    float *__restrict__ cut_vals, float *__restrict__ probs, const uint32_t *__restrict__ excl) {
   constexpr int TR = 16 * RM;
   // LDS stage: KS of a chunk's 64 k at a time (the chunk accumulator runs across its stages), so
   // that four workgroups fit a CU
@@ -160,12 +217,13 @@ __global__ __launch_bounds__(ONT) void out_tile_kernel(
     const int gr = rb + ty * RM + j;
     if (gr >= R) continue;
     const uint32_t word = bits[(int64_t)gr * VW + (n0 >> 5)];  // n0 % 4 == 0: one word for all 4
+    const uint32_t xword = POOL ? excl[(int64_t)gr * VW + (n0 >> 5)] : word;
     uint32_t key[4];
     float p[4];
 #pragma unroll
     for (int e = 0; e < 4; ++e) {
       p[e] = detm::det_sigmoid32(addf(tot[j][e], bias[e]));
-      key[e] = tiles::key_of(p[e], (word >> ((n0 + e) & 31)) & 1u);
+      key[e] = tiles::key_of(p[e], (xword >> ((n0 + e) & 31)) & 1u);
     }
     uint32_t *kr = keys + (int64_t)gr * Vs + n0;  // Vs % 4 == 0: 16-B aligned, the pad is ours
     *reinterpret_cast<uint4 *>(kr) = make_uint4(key[0], key[1], key[2], key[3]);
@@ -229,12 +287,17 @@ __device__ __forceinline__ void bitonic_sort_desc(uint64_t *a, int P) {
     }
 }
 
+// POOL: the row's candidates are the n_cand[r] cards whose exclusion bit is clear (row_mask_kernel),
+// and every other card has key' = 0: want <= n_cand[r], so the want-th largest composite is a
+// candidate's, the select's threshold has key' != 0 and no excluded card passes it.
+template <bool POOL>
 __global__ __launch_bounds__(SNT) void topn_rows_kernel(const uint32_t *__restrict__ keys, int Vs,
                                                         int V, const int32_t *__restrict__ row_ptr,
                                                         int amount, int A,
                                                         int32_t *__restrict__ n_add,
                                                         int32_t *__restrict__ additions,
-                                                        float *__restrict__ add_vals) {
+                                                        float *__restrict__ add_vals,
+                                                        const int32_t *__restrict__ n_cand) {
   __shared__ uint32_t hist[1024];
   __shared__ int wtot[SNT / 64];
   __shared__ uint64_t s_prefix, s_mask;
@@ -242,8 +305,8 @@ __global__ __launch_bounds__(SNT) void topn_rows_kernel(const uint32_t *__restri
   __shared__ uint64_t sel[MAX_AMOUNT];
   const int tid = threadIdx.x;
   const int r = blockIdx.x;
-  const int n = row_ptr[r + 1] - row_ptr[r];
-  const int want = max(0, min(min(amount > 0 ? amount : 1, V - n), MAX_AMOUNT));
+  const int cand = POOL ? n_cand[r] : V - (row_ptr[r + 1] - row_ptr[r]);
+  const int want = max(0, min(min(amount > 0 ? amount : 1, cand), MAX_AMOUNT));
   int32_t *adds = additions + (int64_t)r * A;
   float *addv = add_vals + (int64_t)r * A;
   for (int i = want + tid; i < A; i += SNT) {  // the unused tail
@@ -315,7 +378,9 @@ __global__ __launch_bounds__(SNT) void topn_rows_kernel(const uint32_t *__restri
 // through pa / pb as one 64-bit word; the last pass stores nothing but the row's results:
 // ascending position pos is descending position V - 1 - pos, and the cube cards (key' = 0) hold
 // the first n ascending positions, i.e. the last n descending ones, which want <= V - n never
-// reaches.
+// reaches.  POOL: the excluded cards (cube or outside the pool, key' = 0) hold the first
+// V - n_cand[r] ascending positions, the last V - n_cand[r] descending ones, which
+// want <= n_cand[r] never reaches.
 __device__ __forceinline__ uint64_t rank_load(const uint32_t *k, const uint64_t *src, int pass,
                                                int i) {
   return pass == 0 ? ((uint64_t)k[i] << 32) | (uint32_t)i : src[i];
@@ -333,21 +398,23 @@ __device__ __forceinline__ uint64_t rank_match(uint32_t dg, bool valid, int nbit
 }
 constexpr int RU = 8;  // items a lane loads ahead of ranking them: the loads' latency is paid once
 
+template <bool POOL>
 __global__ __launch_bounds__(SNT) void rank_rows_kernel(const uint32_t *__restrict__ keys, int Vs,
                                                         int V, const int32_t *__restrict__ row_ptr,
                                                         int amount, int A, uint64_t *pa,
                                                         uint64_t *pb, int Vp,
                                                         int32_t *__restrict__ n_add,
                                                         int32_t *__restrict__ additions,
-                                                        float *__restrict__ add_vals) {
+                                                        float *__restrict__ add_vals,
+                                                        const int32_t *__restrict__ n_cand) {
   constexpr int NW = SNT / 64;
   __shared__ uint32_t hist[NW * tiles::R];  // [wave][digit]: a thread scans its digit's column
   __shared__ int wtot[NW];
   const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
   const uint64_t lt = (1ull << lane) - 1ull;
   const int r = blockIdx.x;
-  const int n = row_ptr[r + 1] - row_ptr[r];
-  const int want = max(0, min(amount > 0 ? amount : 1, V - n));
+  const int cand = POOL ? n_cand[r] : V - (row_ptr[r + 1] - row_ptr[r]);
+  const int want = max(0, min(amount > 0 ? amount : 1, cand));
   int32_t *adds = additions + (int64_t)r * A;
   float *addv = add_vals + (int64_t)r * A;
   for (int i = want + tid; i < A; i += SNT) {  // the unused tail
@@ -610,13 +677,40 @@ BatchWs batch_ws(int V, int d, int R, int max_n) {
   return w;
 }
 
+// the pooled entries' share of the workspace, behind the batch workspace:
+// [exclusion bitmasks R*VW][n_cand R]
+struct PoolWs {
+  size_t excl, ncand, total;
+};
+PoolWs pool_ws(const BatchWs &w, int R) {
+  PoolWs p;
+  const size_t r = (size_t)std::max(R, 1);
+  size_t o = w.total;
+  p.excl = o, o += tiles::align256(r * w.VW * sizeof(uint32_t));
+  p.ncand = o, o += tiles::align256(r * sizeof(int32_t));
+  p.total = o;
+  return p;
+}
+
+// A pooled call's extra arguments (device pointers); the unpooled entries pass none.
+struct Pools {
+  const uint32_t *pools;
+  int n_pools;
+  const int32_t *pool_of_row;
+};
+
 template <int RM>
 void launch_out(dim3 grid, hipStream_t s, const float *h3, const float *Wo, const float *bo, int d,
                 int V, int R, const int32_t *row_ptr, const int32_t *idx, const uint32_t *bits,
-                int VW, uint32_t *keys, int Vs, float *cut_vals, float *probs) {
+                int VW, uint32_t *keys, int Vs, float *cut_vals, float *probs,
+                const uint32_t *excl) {
   grid.y = (unsigned)cdiv(R, 16 * RM);
-  hipLaunchKernelGGL(out_tile_kernel<RM>, grid, dim3(ONT), 0, s, h3, Wo, bo, d, V, R, row_ptr, idx,
-                     bits, VW, keys, Vs, cut_vals, probs);
+  if (excl)
+    hipLaunchKernelGGL((out_tile_kernel<RM, true>), grid, dim3(ONT), 0, s, h3, Wo, bo, d, V, R,
+                       row_ptr, idx, bits, VW, keys, Vs, cut_vals, probs, excl);
+  else
+    hipLaunchKernelGGL((out_tile_kernel<RM, false>), grid, dim3(ONT), 0, s, h3, Wo, bo, d, V, R,
+                       row_ptr, idx, bits, VW, keys, Vs, cut_vals, probs, excl);
 }
 
 }  // namespace
@@ -627,18 +721,31 @@ extern "C" size_t cc_recommend_batch_ws_size(int32_t V, int32_t d, int32_t R, in
   return batch_ws(V, d, R, max_n).total + 256;
 }
 
-// The launches both entries share: cube bitmasks, h3, then the output layer, which leaves every
-// row's sort keys in the workspace, its cut values and (on request) its probabilities.
+// The launches all entries share: row masks, h3, then the output layer, which leaves every row's
+// sort keys in the workspace, its cut values and (on request) its probabilities.  pl: a pooled
+// call's arguments, or null; *n_cand then points at the rows' candidate counts, or is null.
 static int batch_keys_launch(const float *params, int V, int d, int R, const int32_t *row_ptr,
                              const int32_t *idx, int max_n, void *ws, const BatchWs &w,
-                             float *cut_vals, float *probs, hipStream_t s) {
+                             float *cut_vals, float *probs, hipStream_t s,
+                             const Pools *pl = nullptr, const int32_t **n_cand = nullptr) {
   int64_t off[CC_NUM_TENSORS], sz[CC_NUM_TENSORS], tot, mt;
   if (int rc = cc::param_offsets(V, d, off, sz, &tot, &mt)) return rc;
   char *base = (char *)ws;
   float *h3 = (float *)(base + w.h3);
   uint32_t *keys = (uint32_t *)(base + w.keys), *bits = (uint32_t *)(base + w.bits);
-  hipLaunchKernelGGL(row_bits_kernel, dim3(R), dim3(256), 0, s, row_ptr, idx, V, w.VW, bits);
-  CC_LAUNCH_CHECK("row_bits_kernel");
+  const uint32_t *excl = nullptr;
+  if (pl) {
+    const PoolWs p = pool_ws(w, R);
+    excl = (const uint32_t *)(base + p.excl);
+    *n_cand = (const int32_t *)(base + p.ncand);
+    hipLaunchKernelGGL(row_mask_kernel, dim3(R), dim3(256), 0, s, row_ptr, idx, V, w.VW, pl->pools,
+                       pl->n_pools, pl->pool_of_row, bits, (uint32_t *)(base + p.excl),
+                       (int32_t *)(base + p.ncand));
+    CC_LAUNCH_CHECK("row_mask_kernel");
+  } else {
+    hipLaunchKernelGGL(row_bits_kernel, dim3(R), dim3(256), 0, s, row_ptr, idx, V, w.VW, bits);
+    CC_LAUNCH_CHECK("row_bits_kernel");
+  }
   if (int rc = cc::infer_h3_launch(params, V, d, R, row_ptr, idx, max_n, (float *)(base + w.part),
                                    (float *)(base + w.zlat), h3, s))
     return rc;
@@ -646,12 +753,21 @@ static int batch_keys_launch(const float *params, int V, int d, int R, const int
   const dim3 grid((unsigned)cdiv(V, TC), 1);
   // rows per tile: 32 / 64 / 128 (the arithmetic per (row, card) does not depend on it)
   if (R <= 32)
-    launch_out<2>(grid, s, h3, Wo, bo, d, V, R, row_ptr, idx, bits, w.VW, keys, w.Vs, cut_vals, probs);
+    launch_out<2>(grid, s, h3, Wo, bo, d, V, R, row_ptr, idx, bits, w.VW, keys, w.Vs, cut_vals, probs, excl);
   else if (R <= 64)
-    launch_out<4>(grid, s, h3, Wo, bo, d, V, R, row_ptr, idx, bits, w.VW, keys, w.Vs, cut_vals, probs);
+    launch_out<4>(grid, s, h3, Wo, bo, d, V, R, row_ptr, idx, bits, w.VW, keys, w.Vs, cut_vals, probs, excl);
   else
-    launch_out<8>(grid, s, h3, Wo, bo, d, V, R, row_ptr, idx, bits, w.VW, keys, w.Vs, cut_vals, probs);
+    launch_out<8>(grid, s, h3, Wo, bo, d, V, R, row_ptr, idx, bits, w.VW, keys, w.Vs, cut_vals, probs, excl);
   CC_LAUNCH_CHECK("out_tile_kernel");
+  return CC_OK;
+}
+
+// The pooled entries' own argument checks (who: the entry's name).
+static int pools_check(const std::string &who, const uint32_t *pools, int n_pools,
+                       const int32_t *pool_of_row) {
+  CC_REQUIRE(pool_of_row, who + ": null pointer");
+  CC_REQUIRE(n_pools >= 0, who + ": n_pools is negative");
+  CC_REQUIRE(pools || n_pools == 0, who + ": pools is null with n_pools > 0");
   return CC_OK;
 }
 
@@ -673,9 +789,46 @@ extern "C" int cc_recommend_batch_fp32(const float *params, int32_t V, int32_t d
   if (int rc = batch_keys_launch(params, V, d, R, row_ptr, idx, max_n, ws, w, cut_vals, probs, s))
     return rc;
   const int A = amount > 0 ? amount : 1;
-  hipLaunchKernelGGL(topn_rows_kernel, dim3(R), dim3(SNT), 0, s,
+  hipLaunchKernelGGL(topn_rows_kernel<false>, dim3(R), dim3(SNT), 0, s,
                      (const uint32_t *)((char *)ws + w.keys), w.Vs, V, row_ptr, amount, A, n_add,
-                     additions, add_vals);
+                     additions, add_vals, (const int32_t *)nullptr);
+  CC_LAUNCH_CHECK("topn_rows_kernel");
+  return CC_OK;
+}
+
+extern "C" size_t cc_recommend_batch_pool_ws_size(int32_t V, int32_t d, int32_t R, int32_t max_n) {
+  return pool_ws(batch_ws(V, d, R, max_n), R).total + 256;
+}
+
+extern "C" int cc_recommend_batch_pool_fp32(const float *params, int32_t V, int32_t d, int32_t R,
+                                            const int32_t *row_ptr, const int32_t *idx,
+                                            int32_t max_n, int32_t amount, void *ws,
+                                            int32_t *n_add, int32_t *additions, float *add_vals,
+                                            float *cut_vals, float *probs, const uint32_t *pools,
+                                            int32_t n_pools, const int32_t *pool_of_row,
+                                            void *stream) {
+  CC_REQUIRE(params && row_ptr && idx && ws && n_add && additions && add_vals && cut_vals,
+             "cc_recommend_batch_pool_fp32: null pointer");
+  if (int rc = pools_check("cc_recommend_batch_pool_fp32", pools, n_pools, pool_of_row)) return rc;
+  CC_REQUIRE(V > 0 && R >= 0 && max_n >= 0 && max_n <= V,
+             "cc_recommend_batch_pool_fp32: V/R/max_n");
+  if (int rc = cc::infer_check_d(d, "cc_recommend_batch_pool_fp32")) return rc;
+  CC_REQUIRE(amount <= MAX_AMOUNT,
+             "cc_recommend_batch_pool_fp32: amount above cc_recommend_batch_max_amount()");
+  CC_REQUIRE(((uintptr_t)ws & 255) == 0,
+             "cc_recommend_batch_pool_fp32: ws must be 256-byte aligned");
+  if (R == 0) return CC_OK;
+  const BatchWs w = batch_ws(V, d, R, max_n);
+  hipStream_t s = as_stream(stream);
+  const Pools pl{pools, n_pools, pool_of_row};
+  const int32_t *n_cand = nullptr;
+  if (int rc = batch_keys_launch(params, V, d, R, row_ptr, idx, max_n, ws, w, cut_vals, probs, s,
+                                 &pl, &n_cand))
+    return rc;
+  const int A = amount > 0 ? amount : 1;
+  hipLaunchKernelGGL(topn_rows_kernel<true>, dim3(R), dim3(SNT), 0, s,
+                     (const uint32_t *)((char *)ws + w.keys), w.Vs, V, row_ptr, amount, A, n_add,
+                     additions, add_vals, n_cand);
   CC_LAUNCH_CHECK("topn_rows_kernel");
   return CC_OK;
 }
@@ -711,9 +864,48 @@ extern "C" int cc_recommend_batch_rank_fp32(const float *params, int32_t V, int3
   char *base = (char *)ws;
   uint64_t *pa = (uint64_t *)(base + w.total), *pb = (uint64_t *)(base + w.total + rank_buf_bytes(V, R));
   const int A = std::min(amount > 0 ? amount : 1, V);
-  hipLaunchKernelGGL(rank_rows_kernel, dim3(R), dim3(SNT), 0, s, (const uint32_t *)(base + w.keys),
-                     w.Vs, V, row_ptr, amount, A, pa, pb, (int)rank_pitch(V), n_add, additions,
-                     add_vals);
+  hipLaunchKernelGGL(rank_rows_kernel<false>, dim3(R), dim3(SNT), 0, s,
+                     (const uint32_t *)(base + w.keys), w.Vs, V, row_ptr, amount, A, pa, pb,
+                     (int)rank_pitch(V), n_add, additions, add_vals, (const int32_t *)nullptr);
+  CC_LAUNCH_CHECK("rank_rows_kernel");
+  return CC_OK;
+}
+
+// pooled rank workspace: the batch workspace, the pool's share, then the ping-pong buffers
+extern "C" size_t cc_recommend_batch_rank_pool_ws_size(int32_t V, int32_t d, int32_t R,
+                                                       int32_t max_n) {
+  return pool_ws(batch_ws(V, d, R, max_n), R).total + 2 * rank_buf_bytes(V, R) + 256;
+}
+
+extern "C" int cc_recommend_batch_rank_pool_fp32(
+    const float *params, int32_t V, int32_t d, int32_t R, const int32_t *row_ptr,
+    const int32_t *idx, int32_t max_n, int32_t amount, void *ws, int32_t *n_add,
+    int32_t *additions, float *add_vals, float *cut_vals, float *probs, const uint32_t *pools,
+    int32_t n_pools, const int32_t *pool_of_row, void *stream) {
+  CC_REQUIRE(params && row_ptr && idx && ws && n_add && additions && add_vals && cut_vals,
+             "cc_recommend_batch_rank_pool_fp32: null pointer");
+  if (int rc = pools_check("cc_recommend_batch_rank_pool_fp32", pools, n_pools, pool_of_row))
+    return rc;
+  CC_REQUIRE(V > 0 && R >= 0 && max_n >= 0 && max_n <= V,
+             "cc_recommend_batch_rank_pool_fp32: V/R/max_n");
+  if (int rc = cc::infer_check_d(d, "cc_recommend_batch_rank_pool_fp32")) return rc;
+  CC_REQUIRE(((uintptr_t)ws & 255) == 0,
+             "cc_recommend_batch_rank_pool_fp32: ws must be 256-byte aligned");
+  if (R == 0) return CC_OK;
+  const BatchWs w = batch_ws(V, d, R, max_n);
+  hipStream_t s = as_stream(stream);
+  const Pools pl{pools, n_pools, pool_of_row};
+  const int32_t *n_cand = nullptr;
+  if (int rc = batch_keys_launch(params, V, d, R, row_ptr, idx, max_n, ws, w, cut_vals, probs, s,
+                                 &pl, &n_cand))
+    return rc;
+  char *base = (char *)ws;
+  const size_t after = pool_ws(w, R).total;
+  uint64_t *pa = (uint64_t *)(base + after), *pb = (uint64_t *)(base + after + rank_buf_bytes(V, R));
+  const int A = std::min(amount > 0 ? amount : 1, V);
+  hipLaunchKernelGGL(rank_rows_kernel<true>, dim3(R), dim3(SNT), 0, s,
+                     (const uint32_t *)(base + w.keys), w.Vs, V, row_ptr, amount, A, pa, pb,
+                     (int)rank_pitch(V), n_add, additions, add_vals, n_cand);
   CC_LAUNCH_CHECK("rank_rows_kernel");
   return CC_OK;
 }
@@ -743,6 +935,46 @@ extern "C" int cc_recommend_batch_target_ranks_fp32(
   const BatchWs w = batch_ws(V, d, R, max_n);
   hipStream_t s = as_stream(stream);
   if (int rc = batch_keys_launch(params, V, d, R, row_ptr, idx, max_n, ws, w, cut_vals, probs, s))
+    return rc;
+  hipLaunchKernelGGL(target_ranks_kernel, dim3(R), dim3(SNT), 0, s,
+                     (const uint32_t *)((char *)ws + w.keys), w.Vs, V, tgt_ptr, tgt, cutoffs,
+                     n_cutoffs, ranks, tgt_vals, hits);
+  CC_LAUNCH_CHECK("target_ranks_kernel");
+  return CC_OK;
+}
+
+// The pooled keys give a card outside its row's pool key' = 0, as a cube card has: the counting
+// kernel ranks such a target -1 with value 0 and counts the pool's candidates alone.
+extern "C" size_t cc_recommend_batch_target_ranks_pool_ws_size(int32_t V, int32_t d, int32_t R,
+                                                               int32_t max_n) {
+  return pool_ws(batch_ws(V, d, R, max_n), R).total + 256;
+}
+
+extern "C" int cc_recommend_batch_target_ranks_pool_fp32(
+    const float *params, int32_t V, int32_t d, int32_t R, const int32_t *row_ptr,
+    const int32_t *idx, int32_t max_n, const int32_t *tgt_ptr, const int32_t *tgt,
+    const int32_t *cutoffs, int32_t n_cutoffs, void *ws, int32_t *ranks, float *tgt_vals,
+    unsigned long long *hits, float *cut_vals, float *probs, const uint32_t *pools,
+    int32_t n_pools, const int32_t *pool_of_row, void *stream) {
+  CC_REQUIRE(params && row_ptr && idx && tgt_ptr && tgt && ws && ranks && tgt_vals && cut_vals,
+             "cc_recommend_batch_target_ranks_pool_fp32: null pointer");
+  if (int rc = pools_check("cc_recommend_batch_target_ranks_pool_fp32", pools, n_pools,
+                           pool_of_row))
+    return rc;
+  CC_REQUIRE(V > 0 && R >= 0 && max_n >= 0 && max_n <= V,
+             "cc_recommend_batch_target_ranks_pool_fp32: V/R/max_n");
+  if (int rc = cc::infer_check_d(d, "cc_recommend_batch_target_ranks_pool_fp32")) return rc;
+  CC_REQUIRE(n_cutoffs >= 0 && n_cutoffs <= MAX_CUTOFFS && (n_cutoffs == 0 || cutoffs),
+             "cc_recommend_batch_target_ranks_pool_fp32: n_cutoffs outside 0..8, or cutoffs null");
+  CC_REQUIRE(((uintptr_t)ws & 255) == 0,
+             "cc_recommend_batch_target_ranks_pool_fp32: ws must be 256-byte aligned");
+  if (R == 0) return CC_OK;
+  const BatchWs w = batch_ws(V, d, R, max_n);
+  hipStream_t s = as_stream(stream);
+  const Pools pl{pools, n_pools, pool_of_row};
+  const int32_t *n_cand = nullptr;
+  if (int rc = batch_keys_launch(params, V, d, R, row_ptr, idx, max_n, ws, w, cut_vals, probs, s,
+                                 &pl, &n_cand))
     return rc;
   hipLaunchKernelGGL(target_ranks_kernel, dim3(R), dim3(SNT), 0, s,
                      (const uint32_t *)((char *)ws + w.keys), w.Vs, V, tgt_ptr, tgt, cutoffs,

@@ -9,6 +9,8 @@ evaluate_loss is the other held-out number, the training loss on cubes the model
 Recommender.reconstruction_loss (cc_recommend_batch_loss_fp32) reduces every row's binary
 cross-entropy and argmax on the device, the host takes the means.
 """
+import inspect
+
 import numpy as np
 
 
@@ -109,14 +111,30 @@ def evaluate_loss(model, cubes, targets=None, rows_per_launch=512):
             'n_cubes': R}
 
 
-def evaluate_holdout(model, cubes, ks=(10, 50, 100), hide=0.2, seed=0, min_visible=1, rows_per_launch=512):
+def evaluate_holdout(model, cubes, ks=(10, 50, 100), hide=0.2, seed=0, min_visible=1, rows_per_launch=512,
+                     pool=None):
     """holdout_split -> target_ranks -> metrics_from_ranks.  `model` is a CC_Recommender or a
     Recommender.  The device's own counters come back under 'hits' (uint64 list: targets with
-    rank < K for each K, targets counted, cubes whose best target has rank < ks[0])."""
+    rank < K for each K, targets counted, cubes whose best target has rank < ks[0]).
+
+    pool (one CardPool for every cube, or one CardPool or None per cube): a hidden card is ranked
+    among the cards of its cube's pool alone, where the user could have picked it.  The split is
+    the unpooled one; hidden cards outside their cube's pool are dropped on the host and counted
+    under 'n_targets_outside_pool', the metrics are over the rest.  A model whose target_ranks
+    takes no pool (GraphRecommender) raises ValueError."""
     rec = model.recommender() if hasattr(model, 'recommender') else model
     visible, hidden = holdout_split(cubes, hide=hide, min_visible=min_visible, seed=seed)
-    ranks, _, hits = rec.target_ranks(visible, hidden, cutoffs=ks, rows_per_launch=rows_per_launch)
-    out = metrics_from_ranks(ranks, ks)
+    if pool is None:
+        ranks, _, hits = rec.target_ranks(visible, hidden, cutoffs=ks, rows_per_launch=rows_per_launch)
+        out = metrics_from_ranks(ranks, ks)
+    else:
+        from .recommender import pools_per_row
+        if 'pool' not in inspect.signature(rec.target_ranks).parameters:
+            raise ValueError(f'{type(rec).__name__}.target_ranks takes no pool')
+        kept = [h if p is None else h[p.contains(h)] for h, p in zip(hidden, pools_per_row(pool, len(hidden)))]
+        ranks, _, hits = rec.target_ranks(visible, kept, cutoffs=ks, rows_per_launch=rows_per_launch, pool=pool)
+        out = metrics_from_ranks(ranks, ks)
+        out['n_targets_outside_pool'] = int(sum(len(h) - len(k) for h, k in zip(hidden, kept)))
     if hits is not None:
         out['hits'] = [int(h) for h in hits]
     return out

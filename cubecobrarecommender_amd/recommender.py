@@ -86,6 +86,89 @@ def pack_targets(targets, inputs, V):
     return tgt_ptr, flat.astype(np.int32)
 
 
+def pool_words(ids, V):
+    """Card ids -> the pool's bit row, uint32 [ceil(V / 32)] (pure host code): bit j & 31 of word
+    j >> 5 set for every id j.  Order does not matter, duplicates collapse, the empty pool is legal;
+    bits at or above V stay zero.  Raises ValueError for an id outside [0, V)."""
+    V = int(V)
+    ids = np.asarray(ids, np.int64).reshape(-1)
+    if len(ids) and (ids.min() < 0 or ids.max() >= V):
+        bad = ids[(ids < 0) | (ids >= V)][0]
+        raise ValueError(f'pool card {int(bad)} outside [0, {V})')
+    words = np.zeros((V + 31) // 32, np.uint32)
+    np.bitwise_or.at(words, ids >> 5, np.uint32(1) << (ids & 31).astype(np.uint32))
+    return words
+
+
+class CardPool:
+    """A set of card ids that narrows the candidates of a ranking call: the sorted distinct `ids`,
+    their number `size`, the card count `V` the pool was built for, its bit row `words`
+    (pool_words) and, from Recommender.card_pool, the same words on the device (`words_dev`).
+    Immutable after construction: one pool serves any number of calls and threads."""
+
+    def __init__(self, ids, V, words_dev=None):
+        self.V = int(V)
+        self.words = pool_words(ids, self.V)
+        self.ids = np.unique(np.asarray(ids, np.int64).reshape(-1))
+        self.size = len(self.ids)
+        self.words_dev = words_dev
+
+    def contains(self, cards):
+        """bool array: which of the card ids `cards` are in the pool (none outside [0, V) is)."""
+        cards = np.asarray(cards, np.int64)
+        ok = (cards >= 0) & (cards < self.V)
+        c = np.where(ok, cards, 0)
+        return ok & ((self.words[c >> 5] >> (c & 31).astype(np.uint32)) & 1).astype(bool)
+
+
+def pools_per_row(pool, R):
+    """The `pool` argument of a ranking call (not None) as a list of R entries, each a CardPool or
+    None.  Raises ValueError for a sequence of another length or an entry of another type."""
+    per_row = [pool] * R if isinstance(pool, CardPool) else list(pool)
+    if len(per_row) != R:
+        raise ValueError(f'{len(per_row)} pools for {R} cubes')
+    for r, p in enumerate(per_row):
+        if p is not None and not isinstance(p, CardPool):
+            raise ValueError(f'cube {r}: the pool is {type(p).__name__}, not a CardPool or None')
+    return per_row
+
+
+def resolve_pools(pool, R, V):
+    """The `pool` argument of a ranking call -> (pools, pool_of_row), or (None, None) for no pool
+    at all (pure host code).  `pool` is None, one CardPool for every row, or a sequence of R
+    entries, each a CardPool or None.  pools: the call's distinct CardPools in order of first use;
+    pool_of_row: int32 [R], row r's index into pools, -1 for a row without one.  Raises ValueError
+    for a sequence of another length, an entry that is no CardPool, or a pool built for another V."""
+    if pool is None:
+        return None, None
+    pools, at = [], {}
+    pool_of_row = np.full(R, -1, np.int32)
+    for r, p in enumerate(pools_per_row(pool, R)):
+        if p is None:
+            continue
+        if p.V != V:
+            raise ValueError(f'cube {r}: the pool was built for {p.V} cards, the model has {V}')
+        if id(p) not in at:
+            at[id(p)] = len(pools)
+            pools.append(p)
+        pool_of_row[r] = at[id(p)]
+    if not pools:
+        return None, None
+    return pools, pool_of_row
+
+
+def check_targets_in_pools(targets, pools, pool_of_row):
+    """ValueError for the first target card outside its row's pool, naming the cube and the card
+    (such a card has no rank among the row's candidates).  Ids are already known to be in [0, V)."""
+    for r, t in enumerate(targets):
+        if pool_of_row[r] < 0:
+            continue
+        t = np.asarray(t, np.int64).reshape(-1)
+        out = ~pools[pool_of_row[r]].contains(t)
+        if out.any():
+            raise ValueError(f'cube {r}: target card {int(t[np.flatnonzero(out)[0]])} is outside the pool')
+
+
 def cuts_in_input_order(cut_csr, slot, inputs):
     """cut_csr (aligned with the CSR's idx) -> per cube, the values in the caller's input order
     with duplicates repeated (pure host code)."""
@@ -179,12 +262,35 @@ class Recommender:
         self.stream.synchronize()
         return out
 
+    # ------------------------------------------------------------------ card pools
+    def card_pool(self, ids):
+        """A CardPool of `ids` for this model with its bit row on the device: uploaded once, then
+        passed as `pool=` to recommend / recommend_many / target_ranks any number of times.  Raises
+        ValueError for an id outside [0, V)."""
+        pool = CardPool(ids, self.V)
+        pool.words_dev = torch.from_numpy(pool.words.view(np.int32)).to(self.dev)
+        return pool
+
+    def _pool_table(self, pools):
+        """The call's distinct pools stacked into one device table [n_pools][VW], once per call."""
+        def here(t):     # self.dev may carry no index ('cuda'): then any index of its type is taken as it
+            return t is not None and t.device.type == self.dev.type and self.dev.index in (None, t.device.index)
+        rows = [p.words_dev if here(p.words_dev) else torch.from_numpy(p.words.view(np.int32)).to(self.dev)
+                for p in pools]
+        return torch.stack(rows).contiguous()
+
     # ------------------------------------------------------------------ single-cube request
-    def recommend(self, cube_indices, amount, want_probs=False, want_order=False):
+    def recommend(self, cube_indices, amount, want_probs=False, want_order=False, pool=None):
         """ml_recommend.py:78-108 for one cube.  Returns dict with additions (card idx,
         descending), add_vals, cut_vals (per cube index, input order), and optionally the full
         probability vector / ranking.  Cubes of up to GRAPH_MAX_IDS distinct cards replay the
-        captured request graph (one launch, one D2H); larger ones run the same kernels directly."""
+        captured request graph (one launch, one D2H); larger ones run the same kernels directly.
+        With a `pool` (a CardPool) the additions are the pool's cards alone and the request takes
+        the batched path, whose rows are bit-identical to this one; want_order with a pool raises."""
+        if pool is not None:
+            if want_order:
+                raise ValueError('want_order is not available with a pool')
+            return self.recommend_many([cube_indices], amount, want_probs=want_probs, pool=pool)[0]
         ci = np.asarray(cube_indices, np.int64)
         uniq = np.unique(ci).astype(np.int32)
         n = len(uniq)
@@ -225,7 +331,7 @@ class Recommender:
         return out
 
     # ------------------------------------------------------------------ many cubes per call
-    def recommend_many(self, cubes, amount, want_probs=False, rows_per_launch=512):
+    def recommend_many(self, cubes, amount, want_probs=False, rows_per_launch=512, pool=None):
         """`recommend` for every cube of `cubes`, bit for bit, in launches of up to
         rows_per_launch rows (cc_recommend_batch_fp32: one pass over the output layer per row
         tile, one ranking workgroup per row).  Returns a list of dicts with the keys and dtypes of
@@ -234,23 +340,33 @@ class Recommender:
         above cc_recommend_batch_max_amount() take cc_recommend_batch_rank_fp32 (one sorting
         workgroup per row, result rows of min(amount, V) entries): its launches are capped by
         rank_rows_per_launch, and their results pass through two pinned staging buffers that the
-        Recommender keeps."""
+        Recommender keeps.
+
+        pool: None, one CardPool (card_pool) for every row, or a sequence of one CardPool or None
+        per cube.  A row with a pool gets, as additions, the first max(amount, 1) members of
+        pool minus cube in the row's unpooled ranking, every value bit for bit the unpooled
+        call's (cc_recommend_batch_pool_fp32 / cc_recommend_batch_rank_pool_fp32); cut_vals and
+        probs do not depend on the pool, nor does the choice of path.  A pool built for another V
+        or a sequence of another length raises ValueError before anything is launched."""
         amount = int(amount)
         rows_per_launch = max(1, int(rows_per_launch))
         inputs = [np.asarray(c, np.int64).reshape(-1) for c in cubes]
         R = len(inputs)
+        pools, pool_of_row = resolve_pools(pool, R, self.V)
         if R == 0:
             return []
         check_card_ids(inputs, self.V)
         V, d, dev = self.V, self.d, self.dev
         rank = amount > int(L.lib().cc_recommend_batch_max_amount())
+        stem = 'cc_recommend_batch_rank' if rank else 'cc_recommend_batch'
+        if pools is not None:
+            stem += '_pool'
+        entry, ws_size = stem + '_fp32', getattr(L.lib(), stem + '_ws_size')
         if rank:
             A = min(max(amount, 1), V)
             rows_per_launch = rank_rows_per_launch(V, A, rows_per_launch, want_probs=want_probs)
-            entry, ws_size = 'cc_recommend_batch_rank_fp32', L.lib().cc_recommend_batch_rank_ws_size
         else:
             A = max(amount, 1)
-            entry, ws_size = 'cc_recommend_batch_fp32', L.lib().cc_recommend_batch_ws_size
         out = []
 
         def staged(t, key):
@@ -276,9 +392,13 @@ class Recommender:
             ints = torch.empty(Rc * (1 + A), device=dev, dtype=torch.int32)      # n_add, additions
             flts = torch.empty(Rc * A + max(nnz, 1), device=dev, dtype=torch.float32)  # add_vals, cuts
             probs = torch.empty(Rc, V, device=dev, dtype=torch.float32) if want_probs else None
+            pool_args = ()
+            if pools is not None:
+                por_d = torch.from_numpy(pool_of_row[r0:r1]).to(dev, non_blocking=True)
+                pool_args = (L.ptr(table), len(pools), L.ptr(por_d))
             L.call(entry, L.ptr(self.params), V, d, Rc, L.ptr(rp_d), L.ptr(ix_d), max_n,
                    amount, L.ptr(self._batch_ws), L.ptr(ints), L.ptr(ints[Rc:]), L.ptr(flts),
-                   L.ptr(flts[Rc * A:]), L.ptr(probs), L.stream_ptr(self.stream))
+                   L.ptr(flts[Rc * A:]), L.ptr(probs), *pool_args, L.stream_ptr(self.stream))
             host = [staged(t, (turn, i))
                     for i, t in enumerate((ints, flts, probs) if want_probs else (ints, flts))]
             done = torch.cuda.Event()
@@ -299,6 +419,7 @@ class Recommender:
                 out.append(o)
 
         with self.lock, torch.cuda.stream(self.stream):
+            table = self._pool_table(pools) if pools is not None else None
             pending = None      # a launch's results are unpacked while the next one runs
             for turn, r0 in enumerate(range(0, R, rows_per_launch)):
                 # a staging set is free again once the launch before last has been collected
@@ -310,7 +431,7 @@ class Recommender:
         return out
 
     # ------------------------------------------------------------------ held-out evaluation
-    def target_ranks(self, cubes, targets, cutoffs=(), rows_per_launch=512):
+    def target_ranks(self, cubes, targets, cutoffs=(), rows_per_launch=512, pool=None):
         """Where the cards of targets[r] land in the ranking `recommend_many(cubes, <all>)` gives
         cube r, without ranking anything (cc_recommend_batch_target_ranks_fp32: the batched
         forward, then one counting workgroup per row; nothing of size R x V comes back).
@@ -321,20 +442,31 @@ class Recommender:
         uint64 array [len(cutoffs) + 2]: targets with rank < cutoffs[k] for each k, then the
         targets counted, then the cubes whose best target has rank < cutoffs[0].  Up to 8
         cutoffs.  An id outside [0, V) in either list, or a target that is also in its cube,
-        raises ValueError before anything is launched."""
+        raises ValueError before anything is launched.
+
+        pool (as for recommend_many): a row with a pool ranks its targets among the pool's cards
+        outside the cube alone, the positions in the pooled `additions`
+        (cc_recommend_batch_target_ranks_pool_fp32); a target outside its row's pool raises
+        ValueError naming the cube and the card, as do a pool built for another V and a sequence
+        of another length, all before anything is launched."""
         rows_per_launch = max(1, int(rows_per_launch))
         cutoffs = [int(k) for k in cutoffs]
         if len(cutoffs) > 8:
             raise ValueError('at most 8 cutoffs')
         inputs = [np.asarray(c, np.int64).reshape(-1) for c in cubes]
         R = len(inputs)
-        V, d, dev = self.V, self.d, self.dev
+        V, d = self.V, self.d
+        pools, pool_of_row = resolve_pools(pool, R, V)
         check_card_ids(inputs, V)
         tgt_ptr, tgt = pack_targets(targets, inputs, V)
+        if pools is not None:
+            check_targets_in_pools(targets, pools, pool_of_row)
         nk = len(cutoffs)
         if R == 0:
             return [], [], (np.zeros(nk + 2, np.uint64) if nk else None)
-        ws_size = L.lib().cc_recommend_batch_target_ranks_ws_size
+        dev = self.dev
+        stem = 'cc_recommend_batch_target_ranks' + ('_pool' if pools is not None else '')
+        entry, ws_size = stem + '_fp32', getattr(L.lib(), stem + '_ws_size')
         ranks, vals = [], []
 
         def launch(r0, r1):
@@ -355,9 +487,14 @@ class Recommender:
             rk = torch.empty(max(nt, 1), device=dev, dtype=torch.int32)
             tv = torch.empty(max(nt, 1), device=dev, dtype=torch.float32)
             cuts = torch.empty(max(nnz, 1), device=dev, dtype=torch.float32)   # the chain's; not returned
-            L.call('cc_recommend_batch_target_ranks_fp32', L.ptr(self.params), V, d, Rc, L.ptr(rp_d),
+            pool_args = ()
+            if pools is not None:
+                por_d = torch.from_numpy(pool_of_row[r0:r1]).to(dev, non_blocking=True)
+                pool_args = (L.ptr(table), len(pools), L.ptr(por_d))
+            L.call(entry, L.ptr(self.params), V, d, Rc, L.ptr(rp_d),
                    L.ptr(ix_d), max_n, L.ptr(tp_d), L.ptr(tg_d), L.ptr(cut_d), nk, L.ptr(self._batch_ws),
-                   L.ptr(rk), L.ptr(tv), L.ptr(hits_d), L.ptr(cuts), None, L.stream_ptr(self.stream))
+                   L.ptr(rk), L.ptr(tv), L.ptr(hits_d), L.ptr(cuts), None, *pool_args,
+                   L.stream_ptr(self.stream))
             host = [torch.empty(t.shape, dtype=t.dtype, pin_memory=True).copy_(t, non_blocking=True)
                     for t in (rk, tv)]
             done = torch.cuda.Event()
@@ -374,6 +511,7 @@ class Recommender:
                 vals.append(tv[lo:hi].copy())
 
         with self.lock, torch.cuda.stream(self.stream):
+            table = self._pool_table(pools) if pools is not None else None
             cut_d = torch.tensor(cutoffs, device=dev, dtype=torch.int32) if nk else None
             hits_d = torch.zeros(nk + 2, device=dev, dtype=torch.int64) if nk else None
             pending = None      # a launch's results are unpacked while the next one runs

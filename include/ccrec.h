@@ -794,6 +794,48 @@ int cc_recommend_batch_target_ranks_fp32(
     const int32_t *cutoffs, int32_t n_cutoffs, void *ws, int32_t *ranks, float *tgt_vals,
     unsigned long long *hits, float *cut_vals, float *probs, void *stream);
 
+/* Card pools: the three calls above with every row's candidates narrowed to a subset of the cards.
+ * Each entry takes the arguments of its unpooled counterpart and, before the stream,
+ *   pools [n_pools][VW] (device), VW = ceil(V / 32): bit j & 31 of word j >> 5 of a row set means
+ *   card j is allowed; bits at or above V are ignored.  NULL with n_pools == 0: no row has a pool.
+ *   pool_of_row [R] (device): the pool of row r, or -1 for none (every card allowed, the unpooled
+ *   result).  Any other value outside [0, n_pools) is never used as an index: that row has no
+ *   candidates.
+ * With S_r the row's cube cards and P_r its pool, the candidates are C_r = P_r \ S_r:
+ *   n_add [r] = min(max(amount, 1), |C_r|) (and at most V on the rank entry); additions / add_vals:
+ *   the first n_add [r] members of C_r in the unpooled ranking of the row, every value bit for bit
+ *   the unpooled call's; the tail -1 / 0 and the row pitch A as in the unpooled call.
+ *   cut_vals and probs do not depend on the pools (every cube card, all V probabilities).
+ *   ranks of a target t in C_r = #{ c in C_r ranked before t }; a target outside C_r (outside
+ *   [0, V), in the cube, or outside the pool) is invalid: ranks = -1, tgt_vals = 0, counted nowhere.
+ *   ws: the entry's own *_pool_ws_size(V, d, R, max_n) bytes (the unpooled workspace plus the rows'
+ *   exclusion bitmasks and candidate counts), 256-B aligned; the call does not depend on its
+ *   contents.
+ * CC_ERR_ARG: as the unpooled entry, and pool_of_row null, n_pools < 0, pools null with
+ * n_pools > 0; nothing is launched or written. */
+size_t cc_recommend_batch_pool_ws_size(int32_t V, int32_t d, int32_t R, int32_t max_n);
+int cc_recommend_batch_pool_fp32(const float *params, int32_t V, int32_t d, int32_t R,
+                                 const int32_t *row_ptr, const int32_t *idx, int32_t max_n,
+                                 int32_t amount, void *ws, int32_t *n_add, int32_t *additions,
+                                 float *add_vals, float *cut_vals, float *probs,
+                                 const uint32_t *pools, int32_t n_pools,
+                                 const int32_t *pool_of_row, void *stream);
+size_t cc_recommend_batch_rank_pool_ws_size(int32_t V, int32_t d, int32_t R, int32_t max_n);
+int cc_recommend_batch_rank_pool_fp32(const float *params, int32_t V, int32_t d, int32_t R,
+                                      const int32_t *row_ptr, const int32_t *idx, int32_t max_n,
+                                      int32_t amount, void *ws, int32_t *n_add,
+                                      int32_t *additions, float *add_vals, float *cut_vals,
+                                      float *probs, const uint32_t *pools, int32_t n_pools,
+                                      const int32_t *pool_of_row, void *stream);
+size_t cc_recommend_batch_target_ranks_pool_ws_size(int32_t V, int32_t d, int32_t R,
+                                                    int32_t max_n);
+int cc_recommend_batch_target_ranks_pool_fp32(
+    const float *params, int32_t V, int32_t d, int32_t R, const int32_t *row_ptr,
+    const int32_t *idx, int32_t max_n, const int32_t *tgt_ptr, const int32_t *tgt,
+    const int32_t *cutoffs, int32_t n_cutoffs, void *ws, int32_t *ranks, float *tgt_vals,
+    unsigned long long *hits, float *cut_vals, float *probs, const uint32_t *pools,
+    int32_t n_pools, const int32_t *pool_of_row, void *stream);
+
 /* Validation loss: the reconstruction output's binary cross-entropy and Keras' categorical-
  * accuracy prediction of R rows, on the logits of cc_recommend_batch_fp32 (the same batched fp32
  * forward and output-layer tile), reduced per row on the device: nothing of size R x V is written.
