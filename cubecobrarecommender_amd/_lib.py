@@ -229,6 +229,8 @@ SIGNATURES = {
     'cc_graph_rec_max_amount': (_I32, []),
     'cc_graph_rec_ws_size': (_SZ, [_I32, _I32, _I32]),
     'cc_graph_rec_f64': (C.c_int, [_P, _I64, _I32, _I32, _P, _P, _I32, _I32, _P, _P, _P, _P, _P, _P, _P]),
+    'cc_graph_rank_ws_size': (_SZ, [_I32, _I32, _I32]),
+    'cc_graph_rank_f64': (C.c_int, [_P, _I64, _I32, _I32, _P, _P, _I32, _I32, _P, _P, _P, _P, _P, _P, _P]),
     'cc_graph_rec_target_ranks_f64': (C.c_int, [_P, _I64, _I32, _I32, _P, _P, _I32, _P, _P, _P, _I32, _P,
                                                 _P, _P, _P, _P, _P, _P]),
 }

@@ -105,13 +105,27 @@ def _cube_cards(cube):
 def simple_recs(cube, adj_mtx, int_to_card=None):
     """src/scripts/recommend.py:7-18: dense 0/1 cube vector in, every missing card out, best
     first (ids, or names with int_to_card).  adj_mtx is the f64 graph or a GraphRecommender; the
-    scores are summed on the GPU (cc_graph_rec_f64), the complete order is the host's
-    argsort(kind='stable')[::-1] of them: descending, equal scores higher index first."""
+    scores are summed and the complete list ordered on the GPU (GraphRecommender.rank_many,
+    cc_graph_rank_f64): descending, equal scores higher index first, argsort(kind='stable')[::-1].
+    An object that offers recommend_many alone gets its scores ordered on the host that way; the
+    list is the same."""
     cube = np.asarray(cube)
-    scores = _graph_of(adj_mtx).recommend_many([_cube_cards(cube)], 1, want_scores=True)[0]['scores']
-    missing = np.where(cube == 0)[0]
-    rec_ids = [int(i) for i in missing[np.argsort(scores[missing], kind='stable')[::-1]]]
+    rec = _graph_of(adj_mtx)
+    if hasattr(rec, 'rank_many'):
+        rec_ids = [int(i) for i in rec.rank_many([_cube_cards(cube)], None, want_vals=False)[0]['additions']]
+    else:
+        scores = rec.recommend_many([_cube_cards(cube)], 1, want_scores=True)[0]['scores']
+        missing = np.where(cube == 0)[0]
+        rec_ids = [int(i) for i in missing[np.argsort(scores[missing], kind='stable')[::-1]]]
     return rec_ids if int_to_card is None else [int_to_card[i] for i in rec_ids]
+
+
+def simple_recs_many(cubes_indices, adj_mtx, int_to_card=None):
+    """`simple_recs` for many cubes given as card-id lists: one complete list per cube (ids, or
+    names with int_to_card) from one GraphRecommender.rank_many call."""
+    outs = _graph_of(adj_mtx).rank_many([list(c) for c in cubes_indices], None, want_vals=False)
+    lists = [[int(i) for i in o['additions']] for o in outs]
+    return lists if int_to_card is None else [[int_to_card[i] for i in ids] for ids in lists]
 
 
 def simple_cuts(cube, adj_mtx, int_to_card=None):
@@ -122,11 +136,21 @@ def simple_cuts(cube, adj_mtx, int_to_card=None):
     return rec_ids if int_to_card is None else [int_to_card[i] for i in rec_ids]
 
 
+def graph_rec_max_amount():
+    """cc_graph_rec_max_amount(): the most additions the graph's select path returns."""
+    from . import _lib
+    return int(_lib.lib().cc_graph_rec_max_amount())
+
+
 def graph_recommend(rec, cube_indices, amount, int_to_card):
     """The co-occurrence baseline in `recommend`'s JSON shape: {"additions": {name: score},
     "cuts": {name: score}} from GraphRecommender `rec`, the additions best first (`amount` of
-    them), the cuts first cut first (every distinct cube card)."""
-    out = rec.recommend_many([list(cube_indices)], amount)[0]
+    them), the cuts first cut first (every distinct cube card).  An amount above
+    cc_graph_rec_max_amount() goes through rec.rank_many where `rec` offers it."""
+    if hasattr(rec, 'rank_many') and int(amount) > graph_rec_max_amount():
+        out = rec.rank_many([list(cube_indices)], amount)[0]
+    else:
+        out = rec.recommend_many([list(cube_indices)], amount)[0]
     output = {'additions': {}, 'cuts': {}}
     for idx, s in zip(out['additions'].tolist(), out['add_vals'].tolist()):
         output['additions'][int_to_card[idx]] = s

@@ -1,4 +1,4 @@
-// cc_graph_rec_f64 / cc_graph_rec_target_ranks_f64 — the co-occurrence baseline (N5): the
+// cc_graph_rec_f64 / cc_graph_rank_f64 / cc_graph_rec_target_ranks_f64 — the co-occurrence baseline (N5): the
 // reference's simple_recs / simple_cuts (src/scripts/recommend.py, cut_cards.py) for R cubes per
 // call on the f64 graph M that cc_adjacency leaves on the device.
 //
@@ -32,6 +32,9 @@
 //                     the want-th largest (10-bit digits from the top of the key, then of the
 //                     card; stops once the chosen bin holds exactly the remaining count), then a
 //                     bitonic sort of the at most MAX_AMOUNT survivors in LDS as (key, card) pairs.
+//   graph_rank_kernel : cc_graph_rank_f64's ranking of every card: recbatch.hip's rank_rows_kernel
+//                     on the 64-bit key, a stable LSD radix sort of (key, card) in 7 passes
+//                     (see the kernel).
 //   graph_target_ranks_kernel : one workgroup per row, one wave per target at a time: the rank is
 //                     a plain count of the cards whose (key, card) is above the target's over the
 //                     row's keys (V * 8 bytes from L2 against the n * V * 8 the scoring pass read).
@@ -344,8 +347,167 @@ __global__ __launch_bounds__(SNT) void graph_target_ranks_kernel(
   }
 }
 
+// Full ranking of one row: recbatch.hip's rank_rows_kernel on the graph's 64-bit key.  A stable
+// LSD radix sort of ascending (key, card) from ascending card order, RANK_PASSES passes of
+// tiles::BITS bits (6 x 10, then the top 4), one workgroup per row.  Wave w owns a contiguous
+// slice of the current arrangement; inside a wave the rank is a ballot multisplit, across waves
+// the exclusive scan of the (digit, wave) counts in digit-major order: no atomics, one order on
+// every run.  Pass 0 reads the row's keys (the card is the index); later passes ping-pong the
+// key and the card through two parallel arrays each (ka / ca, kb / cb).  The last pass stores
+// nothing but the row's results: ascending position pos is descending position V - 1 - pos, and
+// the cube cards (key 0, below every finite score's key) hold the first n ascending positions,
+// i.e. the last n descending ones, which want <= V - n never reaches.
+constexpr int RANK_PASSES = 7;
+constexpr int RANK_U = 8;  // items a lane loads ahead of ranking them
+static_assert(SNT == tiles::R, "a thread scans its digit's column");
+
+__device__ __forceinline__ uint32_t rank_digit(uint64_t key, int pass) {
+  return (uint32_t)(key >> (tiles::BITS * pass)) & (uint32_t)(tiles::R - 1);
+}
+// the valid lanes of the wave that hold digit dg (a value below 2^nbits)
+__device__ __forceinline__ uint64_t rank_match(uint32_t dg, bool valid, int nbits) {
+  uint64_t m = __ballot(valid);
+  for (int bit = 0; bit < nbits; ++bit) {
+    const bool b = (dg >> bit) & 1u;
+    const uint64_t bb = __ballot(b);
+    m &= b ? bb : ~bb;
+  }
+  return m;
+}
+
+__global__ __launch_bounds__(SNT) void graph_rank_kernel(
+    const uint64_t *__restrict__ keys, int Vs, int V, const int32_t *__restrict__ row_ptr,
+    int amount, int A, uint64_t *ka, uint64_t *kb, uint32_t *ca, uint32_t *cb, int Vp,
+    int32_t *__restrict__ n_add, int32_t *__restrict__ additions, double *__restrict__ add_vals) {
+  constexpr int NW = SNT / 64;
+  __shared__ uint32_t hist[NW * tiles::R];  // [wave][digit]: a thread scans its digit's column
+  __shared__ int wtot[NW];
+  const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+  const uint64_t lt = (1ull << lane) - 1ull;
+  const int r = blockIdx.x;
+  const int n = row_ptr[r + 1] - row_ptr[r];
+  const int want = max(0, min(amount > 0 ? amount : 1, V - n));
+  int32_t *adds = additions + (int64_t)r * A;
+  double *addv = add_vals ? add_vals + (int64_t)r * A : nullptr;
+  for (int i = want + tid; i < A; i += SNT) {  // the unused tail
+    adds[i] = -1;
+    if (addv) addv[i] = 0.0;
+  }
+  if (tid == 0) n_add[r] = want;
+  if (want == 0) return;
+  const uint64_t *k = keys + (int64_t)r * Vs;
+  uint64_t *ka_r = ka + (int64_t)r * Vp, *kb_r = kb + (int64_t)r * Vp;
+  uint32_t *ca_r = ca + (int64_t)r * Vp, *cb_r = cb + (int64_t)r * Vp;
+  const int S = (int)cdiv(cdiv(V, NW), 64) * 64;  // per-wave slice
+  const int lo = min(V, w * S), hi = min(V, lo + S);
+  uint32_t *hw = hist + w * tiles::R;
+  for (int pass = 0; pass < RANK_PASSES; ++pass) {
+    const uint64_t *ksrc = pass == 0 ? k : (pass & 1) ? ka_r : kb_r;
+    const uint32_t *csrc = (pass & 1) ? ca_r : cb_r;  // pass 0: the card is the index
+    uint64_t *kdst = (pass & 1) ? kb_r : ka_r;
+    uint32_t *cdst = (pass & 1) ? cb_r : ca_r;
+    const bool last = pass == RANK_PASSES - 1;
+    const int nbits = last ? 64 - tiles::BITS * (RANK_PASSES - 1) : tiles::BITS;
+#pragma unroll
+    for (int i = 0; i < NW; ++i) hist[i * tiles::R + tid] = 0u;
+    __syncthreads();
+    for (int base0 = lo; base0 < hi; base0 += 64 * RANK_U) {
+      uint64_t key[RANK_U];
+#pragma unroll
+      for (int u = 0; u < RANK_U; ++u) {
+        const int i = base0 + 64 * u + lane;
+        key[u] = i < hi ? ksrc[i] : 0ull;
+      }
+#pragma unroll
+      for (int u = 0; u < RANK_U; ++u) {
+        if (base0 + 64 * u >= hi) break;
+        const bool valid = base0 + 64 * u + lane < hi;
+        const uint32_t dg = rank_digit(key[u], pass);
+        const uint64_t m = rank_match(dg, valid, nbits);
+        if (valid && (m & lt) == 0) hw[dg] += (uint32_t)__popcll(m);
+      }
+    }
+    __syncthreads();
+    {  // exclusive scan in (digit, wave) order; thread tid owns digit tid
+      uint32_t c[NW];
+      int s = 0;
+#pragma unroll
+      for (int i = 0; i < NW; ++i) {
+        c[i] = hist[i * tiles::R + tid];
+        s += (int)c[i];
+      }
+      int off = block_incl_scan(s, wtot) - s;
+#pragma unroll
+      for (int i = 0; i < NW; ++i) {
+        hist[i * tiles::R + tid] = (uint32_t)off;
+        off += (int)c[i];
+      }
+    }
+    __syncthreads();
+    for (int base0 = lo; base0 < hi; base0 += 64 * RANK_U) {
+      uint64_t key[RANK_U];
+      uint32_t card[RANK_U];
+#pragma unroll
+      for (int u = 0; u < RANK_U; ++u) {
+        const int i = base0 + 64 * u + lane;
+        key[u] = i < hi ? ksrc[i] : 0ull;
+        card[u] = (pass == 0 || i >= hi) ? (uint32_t)i : csrc[i];
+      }
+#pragma unroll
+      for (int u = 0; u < RANK_U; ++u) {
+        if (base0 + 64 * u >= hi) break;
+        const bool valid = base0 + 64 * u + lane < hi;
+        const uint32_t dg = rank_digit(key[u], pass);
+        const uint64_t m = rank_match(dg, valid, nbits);
+        const uint32_t basepos = hw[dg];
+        const uint32_t pos = basepos + (uint32_t)__popcll(m & lt);
+        if (valid && pos < (uint32_t)V) {  // pos >= V needs inconsistent counts: never write there
+          if (last) {
+            const int q = V - 1 - (int)pos;  // descending position
+            if (q < want) {
+              adds[q] = (int32_t)card[u];
+              if (addv) addv[q] = score_of(key[u]);
+            }
+          } else {
+            kdst[pos] = key[u];
+            cdst[pos] = card[u];
+          }
+        }
+        if (valid && (m & lt) == 0) hw[dg] = basepos + (uint32_t)__popcll(m);
+      }
+    }
+    __threadfence_block();
+    __syncthreads();
+  }
+}
+
 // workspace: the rows' sort keys [R][Vs]; Vs a multiple of 16, so rows start on a 128-byte line
 int key_pitch(int V) { return (std::max(V, 1) + 15) & ~15; }
+
+// the ranking entry's workspace: the keys as above, then the sort's ping-pong arrays, keys
+// [R][Vp] x 2 and cards [R][Vp] x 2; Vp a multiple of 32, so no two rows share a 128-byte line
+// of either
+int rank_pitch(int V) { return (std::max(V, 1) + 31) & ~31; }
+struct RankWs {
+  uint64_t *keys, *ka, *kb;
+  uint32_t *ca, *cb;
+  size_t bytes;
+};
+RankWs rank_ws_of(void *base, int V, int R) {
+  const size_t rows = (size_t)std::max(R, 1);
+  const size_t nk = tiles::align256(rows * key_pitch(V) * sizeof(uint64_t));
+  const size_t np8 = tiles::align256(rows * rank_pitch(V) * sizeof(uint64_t));
+  const size_t np4 = tiles::align256(rows * rank_pitch(V) * sizeof(uint32_t));
+  char *p = (char *)base;
+  RankWs w;
+  w.keys = (uint64_t *)p;
+  w.ka = (uint64_t *)(p + nk);
+  w.kb = (uint64_t *)(p + nk + np8);
+  w.ca = (uint32_t *)(p + nk + 2 * np8);
+  w.cb = (uint32_t *)(p + nk + 2 * np8 + np4);
+  w.bytes = nk + 2 * np8 + 2 * np4 + 256;
+  return w;
+}
 
 template <int CPL, bool VEC, int U>
 void launch_score(int64_t blocks, hipStream_t s, const double *adj, int64_t ld, int V, int R,
@@ -406,6 +568,31 @@ extern "C" int cc_graph_rec_f64(const double *adj, int64_t ld, int32_t V, int32_
   hipLaunchKernelGGL(graph_topn_kernel, dim3(R), dim3(SNT), 0, s, (const uint64_t *)ws,
                      key_pitch(V), V, row_ptr, amount, A, n_add, additions, add_vals);
   CC_LAUNCH_CHECK("graph_topn_kernel");
+  return CC_OK;
+}
+
+extern "C" size_t cc_graph_rank_ws_size(int32_t V, int32_t R, int32_t max_n) {
+  (void)max_n;
+  return rank_ws_of(nullptr, V, R).bytes;
+}
+
+extern "C" int cc_graph_rank_f64(const double *adj, int64_t ld, int32_t V, int32_t R,
+                                 const int32_t *row_ptr, const int32_t *idx, int32_t max_n,
+                                 int32_t amount, void *ws, int32_t *n_add, int32_t *additions,
+                                 double *add_vals, double *cut_vals, double *scores, void *stream) {
+  CC_REQUIRE(adj && row_ptr && idx && ws && n_add && additions && cut_vals,
+             "cc_graph_rank_f64: null pointer");
+  hipStream_t s = as_stream(stream);
+  if (int rc = graph_keys_launch("cc_graph_rank_f64", adj, ld, V, R, row_ptr, idx, max_n, ws,
+                                 cut_vals, scores, s))
+    return rc;
+  if (R == 0) return CC_OK;
+  const int A = std::min(amount > 0 ? amount : 1, V);
+  const RankWs w = rank_ws_of(ws, V, R);
+  hipLaunchKernelGGL(graph_rank_kernel, dim3(R), dim3(SNT), 0, s, (const uint64_t *)w.keys,
+                     key_pitch(V), V, row_ptr, amount, A, w.ka, w.kb, w.ca, w.cb, rank_pitch(V),
+                     n_add, additions, add_vals);
+  CC_LAUNCH_CHECK("graph_rank_kernel");
   return CC_OK;
 }
 

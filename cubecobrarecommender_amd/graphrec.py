@@ -15,7 +15,17 @@ import numpy as np
 import torch
 
 from . import _lib as L
-from .recommender import check_card_ids, pack_cubes, pack_targets
+from .recommender import RANK_STAGING_BYTES, check_card_ids, pack_cubes, pack_targets
+
+
+def graph_rank_rows_per_launch(V, A, rows_per_launch, want_vals=True, want_scores=False,
+                               budget_bytes=RANK_STAGING_BYTES):
+    """Rows per launch of rank_many (pure host code): at most rows_per_launch, at least 1, and as
+    many as keep one launch's pinned staging within budget_bytes.  A row stages n_add and A
+    additions (int32), A values (f64) unless dropped, and V scores (f64) on request; the cut
+    values (one f64 per cube card) are small beside them and not counted."""
+    per_row = 4 + 4 * int(A) + (8 * int(A) if want_vals else 0) + (8 * int(V) if want_scores else 0)
+    return max(1, min(int(rows_per_launch), int(budget_bytes) // per_row))
 
 
 class GraphRecommender:
@@ -42,6 +52,8 @@ class GraphRecommender:
         self.stream = torch.cuda.Stream(device=self.dev)
         self.lock = threading.Lock()
         self._ws = None
+        self._rank_ws = None    # rank_many's workspace (cc_graph_rank_ws_size) ...
+        self._rank_pins = {}    # ... and its two pinned staging sets
         # requests run on the recommender's own stream: the matrix (an upload, or cc_adjacency on
         # another stream) must be complete before they can
         torch.cuda.synchronize(self.dev)
@@ -77,7 +89,8 @@ class GraphRecommender:
 
         A row's bits do not depend on the batch or the launch it falls into.  An id outside
         [0, V) or an amount above cc_graph_rec_max_amount() raises ValueError before anything is
-        launched (the graph path does not rank every card: target_ranks serves evaluation)."""
+        launched (rank_many takes any amount and ranks every card; target_ranks serves
+        evaluation)."""
         amount = int(amount)
         rows_per_launch = max(1, int(rows_per_launch))
         inputs = [np.asarray(c, np.int64).reshape(-1) for c in cubes]
@@ -131,6 +144,91 @@ class GraphRecommender:
             pending = None      # a launch's results are unpacked while the next one runs
             for r0 in range(0, R, rows_per_launch):
                 queued = launch(r0, min(R, r0 + rows_per_launch))
+                if pending is not None:
+                    collect(*pending)
+                pending = queued
+            collect(*pending)
+        return out
+
+    # ------------------------------------------------------------------ every card, ranked
+    def rank_many(self, cubes, amount=None, want_vals=True, want_scores=False, rows_per_launch=512):
+        """`recommend_many` for any amount; amount=None ranks every card (simple_recs' complete
+        list).  cc_graph_rank_f64: the scoring pass, then one sorting workgroup per row.  Returns
+        the list of dicts of recommend_many, bit for bit where both are defined: additions int32 of
+        length min(max(amount, 1), V - n), add_vals f64 (absent with want_vals=False: two thirds
+        of the result bytes), cuts / cut_vals in cut order, scores on request.  Launches are capped
+        by graph_rank_rows_per_launch, and their results pass through two pinned staging sets that
+        the GraphRecommender keeps.  An id outside [0, V) raises ValueError naming the cube before
+        anything is launched."""
+        rows_per_launch = max(1, int(rows_per_launch))
+        inputs = [np.asarray(c, np.int64).reshape(-1) for c in cubes]
+        R = len(inputs)
+        V, dev = self.V, getattr(self, 'dev', None)
+        check_card_ids(inputs, V)
+        if R == 0:
+            return []
+        amount = V if amount is None else int(amount)
+        A = min(max(amount, 1), V)
+        rows_per_launch = graph_rank_rows_per_launch(V, A, rows_per_launch, want_vals, want_scores)
+        if getattr(self, '_rank_pins', None) is None:
+            self._rank_pins = {}
+        pins = self._rank_pins
+        out = []
+
+        def staged(t, key):
+            """A view of the kept pinned buffer `key` (grown when needed) receiving `t`."""
+            if key not in pins or pins[key].numel() < t.numel():
+                pins[key] = torch.empty(t.numel(), dtype=t.dtype, pin_memory=True)
+            return pins[key][:t.numel()].view(t.shape).copy_(t, non_blocking=True)
+
+        def launch(r0, r1, turn):
+            """Pack rows r0..r1, queue their launch and the copies of its results to pinned
+            memory (staging set `turn`); no waiting."""
+            row_ptr, idx, max_n, _, _ = pack_cubes(inputs[r0:r1], V)
+            Rc, nnz = r1 - r0, len(idx)
+            need = int(L.lib().cc_graph_rank_ws_size(V, Rc, max_n)) // 4 + 64
+            if getattr(self, '_rank_ws', None) is None or self._rank_ws.numel() < need:
+                self._rank_ws = torch.empty(need, device=dev, dtype=torch.int32)   # grown when needed, kept
+            rp_d = torch.from_numpy(row_ptr).to(dev, non_blocking=True)
+            ix_d = torch.from_numpy(idx if nnz else np.zeros(1, np.int32)).to(dev, non_blocking=True)
+            ints = torch.empty(Rc * (1 + A), device=dev, dtype=torch.int32)            # n_add, additions
+            vals = torch.empty(Rc * A, device=dev, dtype=torch.float64) if want_vals else None
+            cutv = torch.empty(max(nnz, 1), device=dev, dtype=torch.float64)
+            scores = torch.empty(Rc, V, device=dev, dtype=torch.float64) if want_scores else None
+            L.call('cc_graph_rank_f64', L.ptr(self.adj), self.ld, V, Rc, L.ptr(rp_d), L.ptr(ix_d), max_n,
+                   amount, L.ptr(self._rank_ws), L.ptr(ints), L.ptr(ints[Rc:]), L.ptr(vals), L.ptr(cutv),
+                   L.ptr(scores), L.stream_ptr(self.stream))
+            host = {name: staged(t, (turn, name))
+                    for name, t in (('ints', ints), ('vals', vals), ('cutv', cutv), ('scores', scores))
+                    if t is not None}
+            done = torch.cuda.Event()
+            done.record(self.stream)
+            return r0, r1, row_ptr, idx, host, done
+
+        def collect(r0, r1, row_ptr, idx, host, done):
+            done.synchronize()
+            Rc = r1 - r0
+            got = {name: t.numpy().copy() for name, t in host.items()}     # out of the pinned staging
+            ints, cutv = got['ints'], got['cutv']
+            nadd, adds = ints[:Rc].tolist(), ints[Rc:].reshape(Rc, A)
+            addv = got['vals'].reshape(Rc, A) if want_vals else None
+            for r in range(Rc):
+                k = nadd[r]
+                ids, vals = idx[row_ptr[r]:row_ptr[r + 1]], cutv[row_ptr[r]:row_ptr[r + 1]]
+                order = np.argsort(vals, kind='stable')     # about 360 values: the host's job
+                o = {'additions': adds[r, :k]}
+                if want_vals:
+                    o['add_vals'] = addv[r, :k]
+                o['cuts'], o['cut_vals'] = ids[order], vals[order]
+                if want_scores:
+                    o['scores'] = got['scores'][r]
+                out.append(o)
+
+        with self.lock, torch.cuda.stream(self.stream):
+            pending = None      # a launch's results are unpacked while the next one runs
+            for turn, r0 in enumerate(range(0, R, rows_per_launch)):
+                # a staging set is free again once the launch before last has been collected
+                queued = launch(r0, min(R, r0 + rows_per_launch), turn & 1)
                 if pending is not None:
                     collect(*pending)
                 pending = queued

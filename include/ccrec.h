@@ -910,13 +910,30 @@ int cc_adjacency(const int32_t *row_ptr, const int32_t *idx, int32_t C, int32_t 
  *   per valid target, hits[k] += rank < cutoffs[k] and hits[n_cutoffs] += 1, and
  *   hits[n_cutoffs + 1] += 1 per row whose best valid target has rank < cutoffs[0] (never with
  *   n_cutoffs == 0); integer atomics.  cut_vals, scores, ws as above.
- * CC_ERR_ARG: as above, and n_cutoffs outside 0..8. */
+ * CC_ERR_ARG: as above, and n_cutoffs outside 0..8.
+ *
+ * cc_graph_rank_f64: cc_graph_rec_f64 for any amount: every row is sorted on the device (a stable
+ * radix sort of the 96-bit (key, card), one workgroup per row), so the complete ranking of
+ * simple_recs is one call.  A = min(max(amount, 1), V); n_add [R] = min(max(amount, 1), V - n_r);
+ * additions / add_vals [R][A]: the first n_add[r] entries of the same pinned ranking, the tail
+ * [n_add[r], A) -1 / +0.0.  add_vals may be NULL (not written), scores may be NULL; cut_vals as
+ * above.  ws: cc_graph_rank_ws_size(V, R, max_n) bytes (a multiple of 256, at least
+ * cc_graph_rec_ws_size), 256-B aligned; the call does not depend on its contents.  R == 0
+ * returns CC_OK without a launch.  A row's bits do not depend on R or on what else is in the
+ * batch, and equal cc_graph_rec_f64's wherever both are defined.
+ * CC_ERR_ARG: null pointer (other than add_vals / scores), ld < V, max_n > V, unaligned adj or
+ * ws. */
 int32_t cc_graph_rec_max_amount(void);
 size_t cc_graph_rec_ws_size(int32_t V, int32_t R, int32_t max_n);
 int cc_graph_rec_f64(const double *adj, int64_t ld, int32_t V, int32_t R, const int32_t *row_ptr,
                      const int32_t *idx, int32_t max_n, int32_t amount, void *ws, int32_t *n_add,
                      int32_t *additions, double *add_vals, double *cut_vals, double *scores,
                      void *stream);
+size_t cc_graph_rank_ws_size(int32_t V, int32_t R, int32_t max_n);
+int cc_graph_rank_f64(const double *adj, int64_t ld, int32_t V, int32_t R, const int32_t *row_ptr,
+                      const int32_t *idx, int32_t max_n, int32_t amount, void *ws, int32_t *n_add,
+                      int32_t *additions, double *add_vals, double *cut_vals, double *scores,
+                      void *stream);
 int cc_graph_rec_target_ranks_f64(
     const double *adj, int64_t ld, int32_t V, int32_t R, const int32_t *row_ptr, const int32_t *idx,
     int32_t max_n, const int32_t *tgt_ptr, const int32_t *tgt, const int32_t *cutoffs,

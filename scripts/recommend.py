@@ -4,7 +4,8 @@
 Same arguments, files and output as the reference (recommend.py:20-67): the cube list is fetched,
 output/full_adj_mtx.npy and output/int_to_card.json are read, and the `amount` (default 100) best
 missing cards are printed as "<rank>: <name>".  The column sums and the ranking run on the GPU
-(GraphRecommender).  Extra optional flags: --adj, --id-map, --root."""
+(GraphRecommender; any amount: above the select path's limit every card is sorted on the
+device).  Extra optional flags: --adj, --id-map, --root."""
 import argparse
 import os
 import sys

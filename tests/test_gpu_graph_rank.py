@@ -1,0 +1,252 @@
+"""cc_graph_rank_f64 / GraphRecommender.rank_many / the api's complete lists on the device against
+the numpy statement of the pinned definition (tests/graph_rec_ref.py).  Every comparison is
+exact: f64 bit patterns and integers, np.array_equal, no tolerance anywhere."""
+import numpy as np
+import pytest
+import torch
+
+from cubecobrarecommender_amd import _lib as L
+from cubecobrarecommender_amd import api
+from cubecobrarecommender_amd.graphrec import GraphRecommender
+from cubecobrarecommender_amd.recommender import pack_cubes
+from tests import graph_rec_ref as G
+from tests.test_gpu_graph_rec import GUARD, KINDS, WIDE, bits, device_matrix, edge_cubes, guarded, matrix_of, ref_scores, same
+
+pytestmark = pytest.mark.gpu
+
+# one lane; under, at and just over one wave; under, at and just over one item per thread of the
+# 1024-thread sort; several items per lane with an uneven last wave slice
+SHAPES = [1, 63, 64, 65, 1023, 1024, 1025, 2504]
+_full = {}
+
+
+def full_ranking(V, kind, cubes):
+    """Per edge cube, the complete reference ranking (cards, values), computed once."""
+    if (V, kind) not in _full:
+        want = ref_scores(V, kind, 'edge', cubes)
+        _full[(V, kind)] = [G.additions(s, c, V) for s, c in zip(want, cubes)]
+    return _full[(V, kind)]
+
+
+def rank_direct(buf, ld, V, cubes, amount, want_scores=True, R=None, ws_fill=-1, ws_shift=0, null_vals=False):
+    """cc_graph_rank_f64 itself: outputs pre-filled with junk and guard words behind each, a
+    workspace of exactly cc_graph_rank_ws_size bytes (from ws_shift on) pre-filled with ws_fill
+    words and guard words behind it."""
+    row_ptr, idx, max_n, _, _ = pack_cubes(cubes, V)
+    Rr, nnz, A = len(cubes), len(idx), min(max(amount, 1), V)
+    rp = torch.from_numpy(row_ptr).cuda()
+    ix = torch.from_numpy(idx if nnz else np.zeros(1, np.int32)).cuda()
+    size = int(L.lib().cc_graph_rank_ws_size(V, Rr, max_n))
+    assert size % 256 == 0 and ws_shift % 256 == 0
+    words = (size + ws_shift) // 4
+    ws = torch.full((words + GUARD,), ws_fill, device='cuda', dtype=torch.int32)
+    assert ws.data_ptr() % 256 == 0
+    nadd, adds = guarded(Rr, torch.int32, 77), guarded(Rr * A, torch.int32, 77)
+    addv, cutv = guarded(Rr * A, torch.float64, 7.0), guarded(nnz, torch.float64, 7.0)
+    sc = guarded(Rr * V, torch.float64, 7.0) if want_scores else None
+    rc = L.lib().cc_graph_rank_f64(
+        L.ptr(buf), ld, V, Rr if R is None else R, L.ptr(rp), L.ptr(ix), max_n, amount,
+        L.C.c_void_p(ws.data_ptr() + ws_shift), L.ptr(nadd), L.ptr(adds), None if null_vals else L.ptr(addv),
+        L.ptr(cutv), L.ptr(sc), L.stream_ptr())
+    torch.cuda.synchronize()
+    assert rc == 0, L.lib().cc_last_error_string()
+    w = ws.cpu().numpy()
+    assert np.all(w[words:] == ws_fill), 'guard words behind the workspace'
+    assert np.all(w[:ws_shift // 4] == ws_fill), 'the words before the workspace'
+    out = dict(row_ptr=row_ptr, idx=idx, A=A)
+    for name, t, n, fill in (('nadd', nadd, Rr, 77), ('adds', adds, Rr * A, 77), ('addv', addv, Rr * A, 7.0),
+                             ('cutv', cutv, nnz, 7.0), ('scores', sc, Rr * V, 7.0)):
+        if t is None:
+            continue
+        h = t.cpu().numpy()
+        assert np.all(h[n:] == fill), f'guard words behind {name}'
+        out[name] = h[:n]
+    return out
+
+
+def check_rows(out, V, cubes, want, full, amount, vals=True):
+    """Every output of a direct call against the reference, row by row."""
+    A = out['A']
+    assert A == min(max(amount, 1), V)
+    adds, addv = out['adds'].reshape(len(cubes), A), out['addv'].reshape(len(cubes), A)
+    for r, (cube, s) in enumerate(zip(cubes, want)):
+        k = min(max(amount, 1), V - len(cube))
+        ea, ev = full[r][0][:k], full[r][1][:k]
+        assert len(ea) == k and out['nadd'][r] == k, r
+        assert np.array_equal(adds[r, :k], ea), r
+        assert np.all(adds[r, k:] == -1), r
+        if vals:
+            assert np.array_equal(bits(addv[r, :k]), bits(ev)), r
+            assert np.array_equal(bits(addv[r, k:]), bits(np.zeros(A - k))), r
+        lo, hi = out['row_ptr'][r], out['row_ptr'][r + 1]
+        assert np.array_equal(out['idx'][lo:hi], np.unique(cube))
+        assert np.array_equal(bits(out['cutv'][lo:hi]), bits(s[np.unique(cube)])), r
+        if 'scores' in out:
+            assert np.array_equal(bits(out['scores'].reshape(len(cubes), V)[r]), bits(s)), r
+    if not vals:
+        assert np.all(out['addv'] == 7.0)             # a values buffer that was not passed stays untouched
+
+
+@pytest.mark.parametrize('pad', [0, 3])
+@pytest.mark.parametrize('V', SHAPES)
+def test_direct_call(V, pad):
+    """All five matrices, the edge cubes (n = 0, 1, V - 1 and V among them), every amount, one
+    column per lane in scoring (7 cubes) and two (20 cubes), and once without add_vals."""
+    cap = int(L.lib().cc_graph_rec_max_amount())
+    cubes = edge_cubes(V)
+    assert {0, 1, max(V - 1, 1), V} <= {len(c) for c in cubes[:7]}
+    amounts = sorted({0, 1, 100, cap, cap + 1, V - 1, V, V + 5, 2 ** 31 - 1})
+    for kind in KINDS:
+        M = matrix_of(V, kind)
+        buf, ld = device_matrix(M, pad)
+        want = ref_scores(V, kind, 'edge', cubes)
+        full = full_ranking(V, kind, cubes)
+        if kind == 'sentinel':
+            assert all(np.all(np.abs(s) < 1e29) for s in want)
+        if kind == 'equal':
+            assert np.array_equal(full[0][0], np.arange(V)[::-1])                  # purely by card
+        for amount in amounts:
+            for rows in (len(cubes), 7):
+                assert (rows >= WIDE) == (rows == len(cubes))
+                out = rank_direct(buf, ld, V, cubes[:rows], amount, want_scores=(amount != 1))
+                check_rows(out, V, cubes[:rows], want[:rows], full[:rows], amount)
+        out = rank_direct(buf, ld, V, cubes, V, want_scores=False, null_vals=True)
+        check_rows(out, V, cubes, want, full, V, vals=False)
+
+
+def test_every_key_bit_decides_an_order():
+    """Row 0 holds the 64 single-bit flips of 0.5: with the one-card cube [0] the score of card j
+    is M[0][j] exactly, so the ranking depends on every bit of the key and every digit of every
+    pass; the cube [0, 1] takes the same values through an add (of row 1's zeros)."""
+    V = 130
+    flips = np.array([0x3FE0000000000000 ^ (1 << ((j - 1) % 64)) for j in range(1, V)], np.uint64).view(np.float64)
+    assert np.all(np.isfinite(flips)) and len(np.unique(flips)) == 64
+    assert flips.min() == -0.5 and 8.9e307 < flips.max() < 9e307
+    M = matrix_of(V, 'wild').copy()
+    M[0, 1:] = flips
+    M[1, :] = 0.0
+    cubes = [np.array([0]), np.array([0, 1])]
+    want = [G.scores(M, c) for c in cubes]
+    assert np.array_equal(bits(want[0][1:]), bits(flips)) and np.array_equal(bits(want[1][2:]), bits(flips[1:]))
+    full = [G.additions(s, c, V) for s, c in zip(want, cubes)]
+    # every flip is held by at least two cards: ties go by card, the higher one first
+    order, vals = full[0]
+    assert np.all(np.diff(vals) <= 0) and np.all(np.diff(order)[np.diff(vals) == 0] < 0)
+    assert np.count_nonzero(np.diff(vals) == 0) == V - 1 - 64
+    buf, ld = device_matrix(M, 0)
+    for amount in (V, 2 ** 31 - 1):
+        out = rank_direct(buf, ld, V, cubes, amount)
+        check_rows(out, V, cubes, want, full, amount)
+
+
+@pytest.mark.parametrize('kind', ['wild', 'counts'])
+def test_rows_do_not_depend_on_the_batch(kind):
+    V = 1029
+    rec = GraphRecommender(matrix_of(V, kind))
+    cubes = edge_cubes(V)
+    assert len(cubes) == 20
+    want = ref_scores(V, kind, 'edge', cubes)
+    base = rec.rank_many(cubes)
+    for r, (cube, s, o) in enumerate(zip(cubes, want, base)):
+        ea, ev = G.additions(s, cube, V)
+        ec, ecv = G.cuts(s, cube)
+        assert o['additions'].dtype == np.int32 and o['add_vals'].dtype == np.float64
+        assert o['cuts'].dtype == np.int32 and o['cut_vals'].dtype == np.float64
+        assert np.array_equal(o['additions'], ea) and np.array_equal(bits(o['add_vals']), bits(ev)), r
+        assert np.array_equal(o['cuts'], ec) and np.array_equal(bits(o['cut_vals']), bits(ecv)), r
+    split = rec.rank_many(cubes, rows_per_launch=3)
+    alone = [rec.rank_many([c])[0] for c in cubes]
+    assert len(split) == len(alone) == 20
+    assert all(same(a, b) for a, b in zip(split, base)) and all(same(a, b) for a, b in zip(alone, base))
+
+
+def test_dirty_workspace():
+    V = 1029
+    cubes = edge_cubes(V)
+    buf, ld = device_matrix(matrix_of(V, 'wild'), 0)
+    a = rank_direct(buf, ld, V, cubes, V)
+    b = rank_direct(buf, ld, V, cubes, V, ws_fill=0x5A5A5A5A, ws_shift=256)
+    for name in ('nadd', 'adds', 'addv', 'cutv', 'scores'):
+        assert np.array_equal(a[name].view(np.uint8), b[name].view(np.uint8)), name
+
+
+def test_agreement_with_the_select_path():
+    V = 2504
+    cap = int(L.lib().cc_graph_rec_max_amount())
+    assert V - 120 > cap                                                   # the random cubes' rows fill the cap
+    cubes = edge_cubes(V)
+    for kind in ('counts', 'wild'):
+        rec = GraphRecommender(matrix_of(V, kind))
+        for amount in (1, 100, cap):
+            ranked, selected = rec.rank_many(cubes, amount), rec.recommend_many(cubes, amount)
+            assert len(ranked) == len(selected) == len(cubes)
+            assert all(same(a, b) for a, b in zip(ranked, selected)), (kind, amount)
+            assert len(ranked[-1]['additions']) == amount
+
+
+def test_wrapper():
+    V, kind = 1029, 'wild'
+    M = matrix_of(V, kind)
+    rng = np.random.default_rng(11)
+    cubes = [rng.choice(V, int(rng.integers(1, 300)), replace=True) for _ in range(9)] + [np.array([5, 5, 2, 1000, 2])]
+    assert any(len(np.unique(c)) < len(c) for c in cubes)
+    want = [G.scores(M, c) for c in cubes]
+    rec = GraphRecommender(M)
+    outs = rec.rank_many(cubes, want_scores=True)
+    for c, s, o in zip(cubes, want, outs):
+        ea, ev = G.additions(s, c, V)
+        assert len(o['additions']) == V - len(np.unique(c))                 # amount=None: every missing card
+        assert np.array_equal(o['additions'], ea) and np.array_equal(bits(o['add_vals']), bits(ev))
+        assert np.array_equal(bits(o['scores']), bits(s))
+    bare = rec.rank_many(cubes, want_vals=False)
+    for o, b in zip(outs, bare):
+        assert sorted(b) == ['additions', 'cut_vals', 'cuts']
+        assert same(o, b, ('additions', 'cuts', 'cut_vals'))
+    some = rec.rank_many(cubes, 150)
+    for o, b in zip(outs, some):
+        assert len(b['additions']) == 150 and 'scores' not in b
+        assert np.array_equal(b['additions'], o['additions'][:150])
+        assert np.array_equal(bits(b['add_vals']), bits(o['add_vals'][:150]))
+    buf, ld = device_matrix(M, 3)                                           # a pitched device tensor, in place
+    pitched = GraphRecommender(buf[:, :V])
+    assert pitched.ld == ld and pitched.adj.data_ptr() == buf.data_ptr()
+    assert all(same(a, b) for a, b in zip(pitched.rank_many(cubes), outs))
+    with pytest.raises(ValueError, match=r'cube 1.*outside'):
+        rec.rank_many([[1], [V]])
+
+
+class SelectOnly:
+    """A GraphRecommender that offers recommend_many alone: api.simple_recs' fallback path."""
+
+    def __init__(self, rec):
+        self.recommend_many = rec.recommend_many
+
+
+def test_api():
+    V, kind = 2504, 'counts'
+    M = matrix_of(V, kind)
+    rec = GraphRecommender(M)
+    cap = int(L.lib().cc_graph_rec_max_amount())
+    rng = np.random.default_rng(12)
+    cubes = [rng.choice(V, int(rng.integers(1, 200)), replace=False) for _ in range(5)] + [np.zeros(0, np.int64)]
+    names = {i: f'card {i}' for i in range(V)}
+    loop = []
+    for cards in cubes:
+        vec = np.zeros(V)
+        vec[cards] = 1
+        s = G.scores(M, cards)
+        got = api.simple_recs(vec, rec)
+        assert got == G.additions(s, cards, V)[0].tolist()
+        assert got == api.simple_recs(vec, SelectOnly(rec))
+        assert all(isinstance(i, int) for i in got)
+        loop.append(got)
+    assert api.simple_recs_many(cubes, rec) == loop
+    assert api.simple_recs_many(cubes[:2], rec, names) == [[names[i] for i in ids] for ids in loop[:2]]
+    cards = cubes[0].tolist()
+    s = G.scores(M, cards)
+    out = api.graph_recommend(rec, cards, cap + 1, names)
+    ea, ev = G.additions(s, cards, cap + 1)
+    assert len(out['additions']) == cap + 1 and list(out['additions']) == [names[i] for i in ea]
+    assert list(out['additions'].values()) == ev.tolist()
+    ec, ecv = G.cuts(s, cards)
+    assert list(out['cuts']) == [names[i] for i in ec] and list(out['cuts'].values()) == ecv.tolist()

@@ -10,16 +10,22 @@ the calls visited in turn after a warm-up of each):
           once, so this is graph_score_kernel alone (plus one empty launch)
   ranks : the same call with 20 % of each cube hidden and ranked (the graph here is the whole
           corpus': a timing, not an evaluation)
+  rank  : cc_graph_rank_f64 with amount = V (scoring + the full sort of every row); the sort's own
+          time is rank - score
 and from them: us per cube, and the scoring kernel's gathered bytes, sum_r n_r * V * 8, over its
 time, in TB/s.  The yardstick is the guide's rate for whole rows gathered from HBM into registers,
 5.5-5.8 TB/s; rows that neighbouring cubes share can come from L2 instead, and R = 1 is
 latency-bound (the pinned order forbids splitting a cube's sum).
-`wall` is GraphRecommender.recommend_many end to end (packing, launch, D2H, host cut order), and
-`numpy` the pinned definition on the host: an explicit ascending loop of row adds per cube over
-the same M in host memory, min(R, --host-rows) cubes on 16 threads.  The device scores of those
+`wall` is GraphRecommender.recommend_many end to end (packing, launch, D2H, host cut order);
+`rank_wall` is GraphRecommender.rank_many(cubes) end to end, every card of every cube ranked, and
+`argsort_wall` the same complete lists the way they were made before the device sort:
+recommend_many(cubes, 1, want_scores=True) and a host argsort(kind='stable') per cube, as
+api.simple_recs' fallback does it; the two are timed in turn in the same process and their lists
+compared.  `numpy` is the pinned definition on the host: an explicit ascending loop of row adds per
+cube over the same M in host memory, min(R, --host-rows) cubes on 16 threads.  The device scores of those
 cubes are compared with the host's, bit for bit.  One JSON document on stdout (and in --out).
 
-    python tools/graph_rec_bench.py [--rows 1,64,512] [--repeats 9] [--cubes 65536] [--no-host]
+    python tools/graph_rec_bench.py [--rows 1,64,512] [--repeats 9] [--wall-repeats 5] [--cubes 65536] [--no-host]
 """
 import argparse
 import concurrent.futures as cf
@@ -53,7 +59,7 @@ def host_scores(M, cube):
 
 
 def kernel_times(rec, cubes, repeats):
-    """HIP-event ms per direct call (one launch of all rows): full, score, ranks."""
+    """HIP-event ms per direct call (one launch of all rows): full, score, ranks, rank."""
     dev, R, lib = rec.dev, len(cubes), L.lib()
     rng = np.random.default_rng(1)
     visible, hidden = [], []
@@ -78,7 +84,14 @@ def kernel_times(rec, cubes, repeats):
     cutv = torch.empty(len(idx), device=dev, dtype=torch.float64)
     ranks = torch.empty(max(len(tgt), 1), device=dev, dtype=torch.int32)
     vals = torch.empty(max(len(tgt), 1), device=dev, dtype=torch.float64)
+    rws = torch.empty(int(lib.cc_graph_rank_ws_size(V, R, max_n)) // 4 + 64, device=dev, dtype=torch.int32)
+    radds = torch.empty(R, V, device=dev, dtype=torch.int32)
+    raddv = torch.empty(R, V, device=dev, dtype=torch.float64)
     s = L.stream_ptr()
+
+    def rank():
+        L.call('cc_graph_rank_f64', L.ptr(rec.adj), rec.ld, V, R, L.ptr(rp), L.ptr(ix), max_n, V, L.ptr(rws),
+               L.ptr(nadd), L.ptr(radds), L.ptr(raddv), L.ptr(cutv), None, s)
 
     def full():
         L.call('cc_graph_rec_f64', L.ptr(rec.adj), rec.ld, V, R, L.ptr(rp), L.ptr(ix), max_n, AMOUNT, L.ptr(ws),
@@ -88,7 +101,8 @@ def kernel_times(rec, cubes, repeats):
         L.call('cc_graph_rec_target_ranks_f64', L.ptr(rec.adj), rec.ld, V, R, L.ptr(rp_), L.ptr(ix_), n_,
                L.ptr(t_ptr), L.ptr(tg), None, 0, L.ptr(ws), L.ptr(ranks), L.ptr(vals), None, L.ptr(cutv), None, s)
 
-    calls = {'full': full, 'score': lambda: count(rp, ix, max_n, tp0), 'ranks': lambda: count(vrp, vix, vmax_n, tp)}
+    calls = {'full': full, 'score': lambda: count(rp, ix, max_n, tp0), 'ranks': lambda: count(vrp, vix, vmax_n, tp),
+             'rank': rank}
     times = {m: [] for m in calls}
     for fn in calls.values():
         fn()
@@ -107,6 +121,43 @@ def kernel_times(rec, cubes, repeats):
     out['score_tb_per_s'] = gathered / (out['score']['median'] * 1e-3) / 1e12
     out['score_tb_per_s_best'] = gathered / (out['score']['min'] * 1e-3) / 1e12
     out['us_per_cube'] = out['full']['median'] * 1e3 / R
+    out['sort_ms'] = out['rank']['median'] - out['score']['median']
+    return out
+
+
+def argsort_lists(rec, cubes):
+    """Every cube's complete list from the device's scores and a host argsort per cube
+    (api.simple_recs without rank_many)."""
+    outs = rec.recommend_many(cubes, 1, want_scores=True)
+    lists = []
+    for c, o in zip(cubes, outs):
+        vec = np.zeros(V)
+        vec[c] = 1
+        missing = np.where(vec == 0)[0]
+        lists.append(missing[np.argsort(o['scores'][missing], kind='stable')[::-1]])
+    return lists
+
+
+def complete_list_walls(rec, cubes, repeats):
+    """Wall-clock us per cube of rank_many(cubes) and of argsort_lists, in turn, after a warm-up
+    of each; their lists are compared."""
+    R = len(cubes)
+    ways = {'rank_wall': lambda: [o['additions'] for o in rec.rank_many(cubes)],
+            'argsort_wall': lambda: argsort_lists(rec, cubes)}
+    lists = {m: fn() for m, fn in ways.items()}
+    assert all(np.array_equal(a, b) for a, b in zip(lists['rank_wall'], lists['argsort_wall'])), \
+        'rank_many and the host argsort give different lists'
+    walls = {m: [] for m in ways}
+    for _ in range(repeats):
+        for m, fn in ways.items():                   # alternating
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            fn()
+            walls[m].append((time.perf_counter() - t0) * 1e6 / R)
+    out = {m: {'median': statistics.median(v), 'min': min(v), 'max': max(v)} for m, v in walls.items()}
+    out['lists_equal'] = True
+    out['argsort_over_rank'] = out['argsort_wall']['median'] / out['rank_wall']['median']
+    out['rank_max_below_argsort_min'] = out['rank_wall']['max'] < out['argsort_wall']['min']
     return out
 
 
@@ -114,6 +165,7 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--rows', default='1,64,512')
     ap.add_argument('--repeats', type=int, default=9)
+    ap.add_argument('--wall-repeats', type=int, default=5)
     ap.add_argument('--cubes', type=int, default=65536)
     ap.add_argument('--host-rows', type=int, default=64)
     ap.add_argument('--no-host', action='store_true')
@@ -138,10 +190,16 @@ def main():
                 outs = rec.recommend_many(cubes, AMOUNT)
             wall.append((time.perf_counter() - t0) * 1e6 / (R * max(1, 64 // R)))
         row['wall_us_per_cube'] = {'median': statistics.median(wall), 'min': min(wall), 'max': max(wall)}
+        row['complete_lists_us_per_cube'] = cl = complete_list_walls(rec, cubes, a.wall_repeats)
         line = (f"R={R:4d} n={row['cards_per_cube']:.0f}  ms: full {k['full']['median']:.3f} score "
                 f"{k['score']['median']:.3f} ({k['score']['min']:.3f}..{k['score']['max']:.3f}) ranks "
                 f"{k['ranks']['median']:.3f} -> {k['us_per_cube']:.1f} us/cube, scoring {k['score_tb_per_s']:.2f} TB/s"
-                f" | wall {row['wall_us_per_cube']['median']:.1f} us/cube")
+                f" | wall {row['wall_us_per_cube']['median']:.1f} us/cube"
+                f" | rank {k['rank']['median']:.3f} ({k['rank']['min']:.3f}..{k['rank']['max']:.3f}) ms, sort "
+                f"{k['sort_ms']:.3f} ms | every card: rank_many {cl['rank_wall']['median']:.1f} "
+                f"({cl['rank_wall']['min']:.1f}..{cl['rank_wall']['max']:.1f}) us/cube, host argsort "
+                f"{cl['argsort_wall']['median']:.1f} ({cl['argsort_wall']['min']:.1f}..{cl['argsort_wall']['max']:.1f})"
+                f" us/cube, x{cl['argsort_over_rank']:.1f}")
         if M is not None:
             Rh = min(R, a.host_rows)
             host_scores(M, cubes[0])                 # warm-up: the pages of M
@@ -158,6 +216,8 @@ def main():
             line += f" | numpy {row['numpy_us_per_cube']:.0f} us/cube ({Rh} cubes, 16 threads), bits equal"
         result['rows'][str(R)] = row
         print(line, file=sys.stderr, flush=True)
+        # the gate of the device sort: from 512 cubes its slowest repeat beats the host argsort's fastest
+        assert R < 512 or cl['rank_max_below_argsort_min'], 'rank_many is not faster than the host argsort'
     doc = json.dumps(result)
     if a.out:
         os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
