@@ -77,6 +77,8 @@ template <> struct DT<bf16_t> {
 };
 
 __host__ __device__ static inline int64_t cdiv(int64_t a, int64_t b) { return (a + b - 1) / b; }
+// workspace sections start on 256-byte boundaries
+__host__ __device__ static inline size_t align256(size_t x) { return (x + 255) & ~(size_t)255; }
 
 // ------------------------------------------------------------------ Philox4x32-10 (device)
 struct u32x4 {

@@ -333,7 +333,6 @@ struct CoWs {
   int32_t *ncnt, *acc;
   int64_t *d, *S;
 };
-inline size_t al256(size_t x) { return (x + 255) & ~(size_t)255; }
 inline int64_t chunk_cubes_of(int32_t C, int32_t chunk) {
   int64_t kc = chunk > 0 && chunk < C ? chunk : C;
   return std::min<int64_t>(kc, MAX_CHUNK);
@@ -343,20 +342,20 @@ inline int64_t chunk_bytes(int32_t C, int32_t chunk) {  // Xt row pitch
 }
 inline size_t ws_fixed_bytes(int32_t V, int32_t C, int32_t chunk) {
   const int64_t Kb = chunk_bytes(C, chunk), kc = chunk_cubes_of(C, chunk);
-  return al256((size_t)V * Kb) + al256((size_t)(kc + 1) * 4) + 2 * al256((size_t)V * 8);
+  return align256((size_t)V * Kb) + align256((size_t)(kc + 1) * 4) + 2 * align256((size_t)V * 8);
 }
 inline CoWs co_ws_of(void *base, int32_t V, int32_t C, int32_t chunk) {
   const int64_t Kb = chunk_bytes(C, chunk), kc = chunk_cubes_of(C, chunk);
   char *p = reinterpret_cast<char *>(base);
   CoWs w;
   w.xt = reinterpret_cast<uint8_t *>(p);
-  p += al256((size_t)V * Kb);
+  p += align256((size_t)V * Kb);
   w.ncnt = reinterpret_cast<int32_t *>(p);
-  p += al256((size_t)(kc + 1) * 4);
+  p += align256((size_t)(kc + 1) * 4);
   w.d = reinterpret_cast<int64_t *>(p);
-  p += al256((size_t)V * 8);
+  p += align256((size_t)V * 8);
   w.S = reinterpret_cast<int64_t *>(p);
-  p += al256((size_t)V * 8);
+  p += align256((size_t)V * 8);
   w.acc = reinterpret_cast<int32_t *>(p);
   return w;
 }
@@ -374,7 +373,7 @@ size_t cc_adjacency_ws_size(int32_t V, int32_t C, int32_t chunk_cubes, int32_t w
   size_t b = ws_fixed_bytes(V, C, chunk_cubes);
   // acc (int32 [V][V]) only when cubes come in several chunks and counts is not an output
   // (counts then doubles as the accumulator)
-  if (n_chunks(C, chunk_cubes) > 1 && !with_counts) b += al256((size_t)V * V * 4);
+  if (n_chunks(C, chunk_cubes) > 1 && !with_counts) b += align256((size_t)V * V * 4);
   return b + 256;
 }
 

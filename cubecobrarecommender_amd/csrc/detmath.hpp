@@ -31,6 +31,16 @@ constexpr double INV_LN2 = 0x1.71547652b82fep+0;
 constexpr double TWO_PI = 0x1.921fb54442d18p+2;
 constexpr double SQRT_HALF = 0x1.6a09e667f3bcdp-1;
 
+// The pinned fp32 add and multiply: separately rounded wherever they are inlined.
+__device__ __forceinline__ float addf(float a, float b) {
+#pragma clang fp contract(off)
+  return a + b;
+}
+__device__ __forceinline__ float mulf(float a, float b) {
+#pragma clang fp contract(off)
+  return a * b;
+}
+
 __device__ __forceinline__ double horner(const double *c, int n, double x) {
 #pragma clang fp contract(off)
   double p = c[n - 1];

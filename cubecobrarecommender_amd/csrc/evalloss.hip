@@ -43,14 +43,8 @@ constexpr int ONT = 256;  // output-tile workgroup: 16 card groups x 16 row grou
 // Eigen scalar_logistic_op<float>: exactly 1 from here on (metrics.hip)
 constexpr float SIG_SAT = 15.7243833541870117f;
 
-__device__ __forceinline__ float addf(float a, float b) {
-#pragma clang fp contract(off)
-  return a + b;
-}
-__device__ __forceinline__ float mulf(float a, float b) {
-#pragma clang fp contract(off)
-  return a * b;
-}
+using detm::addf;
+using detm::mulf;
 __device__ __forceinline__ double addd(double a, double b) {
 #pragma clang fp contract(off)
   return a + b;
@@ -227,13 +221,13 @@ LossWs loss_ws(int V, int d, int R, int max_n) {
   w.VW = (std::max(V, 1) + 31) / 32;
   w.tiles = (int)cdiv(std::max(V, 1), TC);
   size_t o = 0;
-  w.part = o, o += tiles::align256(r * cc::infer_gather_cap(max_n) * dd * sizeof(float));
-  w.zlat = o, o += tiles::align256(r * 64 * sizeof(float));
-  w.h3 = o, o += tiles::align256(r * dd * sizeof(float));
-  w.bits = o, o += tiles::align256(r * w.VW * sizeof(uint32_t));
-  w.tloss = o, o += tiles::align256(r * w.tiles * sizeof(double));
-  w.tp = o, o += tiles::align256(r * w.tiles * sizeof(float));
-  w.ti = o, o += tiles::align256(r * w.tiles * sizeof(int32_t));
+  w.part = o, o += align256(r * cc::infer_gather_cap(max_n) * dd * sizeof(float));
+  w.zlat = o, o += align256(r * 64 * sizeof(float));
+  w.h3 = o, o += align256(r * dd * sizeof(float));
+  w.bits = o, o += align256(r * w.VW * sizeof(uint32_t));
+  w.tloss = o, o += align256(r * w.tiles * sizeof(double));
+  w.tp = o, o += align256(r * w.tiles * sizeof(float));
+  w.ti = o, o += align256(r * w.tiles * sizeof(int32_t));
   w.total = o;
   return w;
 }

@@ -32,7 +32,7 @@
 //                     the want-th largest (10-bit digits from the top of the key, then of the
 //                     card; stops once the chosen bin holds exactly the remaining count), then a
 //                     bitonic sort of the at most MAX_AMOUNT survivors in LDS as (key, card) pairs.
-//   graph_rank_kernel : cc_graph_rank_f64's ranking of every card: recbatch.hip's rank_rows_kernel
+//   graph_rank_kernel : cc_graph_rank_f64's ranking of every card: rowsort.hpp's radix_rank_row
 //                     on the 64-bit key, a stable LSD radix sort of (key, card) in 7 passes
 //                     (see the kernel).
 //   graph_target_ranks_kernel : one workgroup per row, one wave per target at a time: the rank is
@@ -43,6 +43,7 @@
 #include <algorithm>
 
 #include "common.hpp"
+#include "rowsort.hpp"
 #include "topn_tiles.hpp"
 
 // build knobs of the scoring kernel's A/B, defaults on: workgroups numbered through
@@ -158,45 +159,19 @@ __global__ __launch_bounds__(GNT) void graph_score_kernel(
   }
 }
 
-// Inclusive scan of one int per thread over the SNT-thread block; wtot: [SNT/64] LDS scratch.
-__device__ __forceinline__ int block_incl_scan(int v, int *wtot) {
-  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-  int x = v;
-#pragma unroll
-  for (int off = 1; off < 64; off <<= 1) {
-    const int y = __shfl_up(x, off, 64);
-    if (lane >= off) x += y;
-  }
-  if (lane == 63) wtot[w] = x;
-  __syncthreads();
-  int before = 0;
-#pragma unroll
-  for (int i = 0; i < SNT / 64; ++i) before += i < w ? wtot[i] : 0;
-  __syncthreads();
-  return before + x;
-}
-
-// Bitonic sort of the pairs (k[i], c[i]), i in [0, P), in LDS, descending, by the whole
-// SNT-thread block; P a power of two, the entries written and a barrier passed before the call.
-__device__ __forceinline__ void bitonic_pairs_desc(uint64_t *k, uint32_t *c, int P) {
-  const int tid = threadIdx.x;
-  for (int size = 2; size <= P; size <<= 1)
-    for (int stride = size >> 1; stride > 0; stride >>= 1) {
-      for (int i = tid; i < P; i += SNT) {
-        const int pr = i ^ stride;
-        if (pr > i) {
-          const bool down = (i & size) == 0;
-          const uint64_t kx = k[i], ky = k[pr];
-          const uint32_t cx = c[i], cy = c[pr];
-          if (pair_gt(ky, cy, kx, cx) == down) {
-            k[i] = ky, c[i] = cy;
-            k[pr] = kx, c[pr] = cx;
-          }
-        }
-      }
-      __syncthreads();
+// Compare-exchange of the pairs (k[i], c[i]) for rowsort::bitonic_sort: descending.
+struct CmpSwapPairs {
+  uint64_t *k;
+  uint32_t *c;
+  __device__ __forceinline__ void operator()(int i, int pr, bool down) const {
+    const uint64_t kx = k[i], ky = k[pr];
+    const uint32_t cx = c[i], cy = c[pr];
+    if (pair_gt(ky, cy, kx, cx) == down) {
+      k[i] = ky, c[i] = cy;
+      k[pr] = kx, c[pr] = cx;
     }
-}
+  }
+};
 
 __global__ __launch_bounds__(SNT) void graph_topn_kernel(const uint64_t *__restrict__ keys, int Vs,
                                                          int V, const int32_t *__restrict__ row_ptr,
@@ -259,7 +234,7 @@ __global__ __launch_bounds__(SNT) void graph_topn_kernel(const uint64_t *__restr
     __syncthreads();
     // thread t owns bin 1023 - t: its inclusive scan is the count of matching items in bins >= it
     const int v = (int)hist[1023 - tid];
-    const int ge = block_incl_scan(v, wtot), gt = ge - v;
+    const int ge = rowsort::block_incl_scan<SNT>(v, wtot), gt = ge - v;
     if (ge >= rem && gt < rem) {  // exactly one bin: the one holding the rem-th largest
       if (on_key) {
         s_kpre = kpre | ((uint64_t)(1023 - tid) << shift);
@@ -287,7 +262,7 @@ __global__ __launch_bounds__(SNT) void graph_topn_kernel(const uint64_t *__restr
   while (P < want) P <<= 1;
   for (int i = min(s_cnt, want) + tid; i < P; i += SNT) selk[i] = 0ull, selc[i] = 0u;  // below every candidate
   __syncthreads();
-  bitonic_pairs_desc(selk, selc, P);
+  rowsort::bitonic_sort<SNT>(P, CmpSwapPairs{selk, selc});
   for (int i = tid; i < want; i += SNT) {
     adds[i] = (int32_t)selc[i];
     addv[i] = score_of(selk[i]);
@@ -347,43 +322,59 @@ __global__ __launch_bounds__(SNT) void graph_target_ranks_kernel(
   }
 }
 
-// Full ranking of one row: recbatch.hip's rank_rows_kernel on the graph's 64-bit key.  A stable
-// LSD radix sort of ascending (key, card) from ascending card order, RANK_PASSES passes of
-// tiles::BITS bits (6 x 10, then the top 4), one workgroup per row.  Wave w owns a contiguous
-// slice of the current arrangement; inside a wave the rank is a ballot multisplit, across waves
-// the exclusive scan of the (digit, wave) counts in digit-major order: no atomics, one order on
-// every run.  Pass 0 reads the row's keys (the card is the index); later passes ping-pong the
-// key and the card through two parallel arrays each (ka / ca, kb / cb).  The last pass stores
-// nothing but the row's results: ascending position pos is descending position V - 1 - pos, and
-// the cube cards (key 0, below every finite score's key) hold the first n ascending positions,
-// i.e. the last n descending ones, which want <= V - n never reaches.
+// Full ranking of one row: rowsort::radix_rank_row on the graph's 64-bit key.  A stable LSD radix
+// sort of ascending (key, card) from ascending card order, RANK_PASSES passes of tiles::BITS bits
+// (6 x 10, then the top 4), one workgroup per row.  Pass 0 reads the row's keys (the card is the
+// index); later passes ping-pong the key and the card through two parallel arrays each (ka / ca,
+// kb / cb).  The last pass stores nothing but the row's results: ascending position pos is
+// descending position V - 1 - pos, and the cube cards (key 0, below every finite score's key) hold
+// the first n ascending positions, i.e. the last n descending ones, which want <= V - n never
+// reaches.
 constexpr int RANK_PASSES = 7;
 constexpr int RANK_U = 8;  // items a lane loads ahead of ranking them
-static_assert(SNT == tiles::R, "a thread scans its digit's column");
 
-__device__ __forceinline__ uint32_t rank_digit(uint64_t key, int pass) {
-  return (uint32_t)(key >> (tiles::BITS * pass)) & (uint32_t)(tiles::R - 1);
-}
-// the valid lanes of the wave that hold digit dg (a value below 2^nbits)
-__device__ __forceinline__ uint64_t rank_match(uint32_t dg, bool valid, int nbits) {
-  uint64_t m = __ballot(valid);
-  for (int bit = 0; bit < nbits; ++bit) {
-    const bool b = (dg >> bit) & 1u;
-    const uint64_t bb = __ballot(b);
-    m &= b ? bb : ~bb;
+struct GraphRankRow {
+  struct Item {
+    uint64_t key;
+    uint32_t card;
+  };
+  static constexpr int PASSES = RANK_PASSES, RADIX_BITS = tiles::BITS;
+  static __device__ constexpr int bits(int pass) {
+    return pass == RANK_PASSES - 1 ? 64 - tiles::BITS * (RANK_PASSES - 1) : tiles::BITS;
   }
-  return m;
-}
+  const uint64_t *k;
+  uint64_t *ka, *kb;
+  uint32_t *ca, *cb;
+  int32_t *adds;
+  double *addv;  // may be null
+  int V, want;
+  __device__ __forceinline__ Item load(int pass, int i) const {
+    if (pass == 0) return {k[i], (uint32_t)i};  // the card is the index
+    return {((pass & 1) ? ka : kb)[i], ((pass & 1) ? ca : cb)[i]};
+  }
+  __device__ __forceinline__ uint32_t digit(const Item &x, int pass) const {
+    return (uint32_t)(x.key >> (tiles::BITS * pass)) & (uint32_t)(tiles::R - 1);
+  }
+  __device__ __forceinline__ void store(int pass, uint32_t pos, const Item &x) const {
+    ((pass & 1) ? kb : ka)[pos] = x.key;
+    ((pass & 1) ? cb : ca)[pos] = x.card;
+  }
+  __device__ __forceinline__ void emit(uint32_t pos, const Item &x) const {
+    const int q = V - 1 - (int)pos;  // descending position
+    if (q < want) {
+      adds[q] = (int32_t)x.card;
+      if (addv) addv[q] = score_of(x.key);
+    }
+  }
+};
 
 __global__ __launch_bounds__(SNT) void graph_rank_kernel(
     const uint64_t *__restrict__ keys, int Vs, int V, const int32_t *__restrict__ row_ptr,
     int amount, int A, uint64_t *ka, uint64_t *kb, uint32_t *ca, uint32_t *cb, int Vp,
     int32_t *__restrict__ n_add, int32_t *__restrict__ additions, double *__restrict__ add_vals) {
-  constexpr int NW = SNT / 64;
-  __shared__ uint32_t hist[NW * tiles::R];  // [wave][digit]: a thread scans its digit's column
-  __shared__ int wtot[NW];
-  const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
-  const uint64_t lt = (1ull << lane) - 1ull;
+  __shared__ uint32_t hist[SNT / 64 * tiles::R];
+  __shared__ int wtot[SNT / 64];
+  const int tid = threadIdx.x;
   const int r = blockIdx.x;
   const int n = row_ptr[r + 1] - row_ptr[r];
   const int want = max(0, min(amount > 0 ? amount : 1, V - n));
@@ -395,90 +386,9 @@ __global__ __launch_bounds__(SNT) void graph_rank_kernel(
   }
   if (tid == 0) n_add[r] = want;
   if (want == 0) return;
-  const uint64_t *k = keys + (int64_t)r * Vs;
-  uint64_t *ka_r = ka + (int64_t)r * Vp, *kb_r = kb + (int64_t)r * Vp;
-  uint32_t *ca_r = ca + (int64_t)r * Vp, *cb_r = cb + (int64_t)r * Vp;
-  const int S = (int)cdiv(cdiv(V, NW), 64) * 64;  // per-wave slice
-  const int lo = min(V, w * S), hi = min(V, lo + S);
-  uint32_t *hw = hist + w * tiles::R;
-  for (int pass = 0; pass < RANK_PASSES; ++pass) {
-    const uint64_t *ksrc = pass == 0 ? k : (pass & 1) ? ka_r : kb_r;
-    const uint32_t *csrc = (pass & 1) ? ca_r : cb_r;  // pass 0: the card is the index
-    uint64_t *kdst = (pass & 1) ? kb_r : ka_r;
-    uint32_t *cdst = (pass & 1) ? cb_r : ca_r;
-    const bool last = pass == RANK_PASSES - 1;
-    const int nbits = last ? 64 - tiles::BITS * (RANK_PASSES - 1) : tiles::BITS;
-#pragma unroll
-    for (int i = 0; i < NW; ++i) hist[i * tiles::R + tid] = 0u;
-    __syncthreads();
-    for (int base0 = lo; base0 < hi; base0 += 64 * RANK_U) {
-      uint64_t key[RANK_U];
-#pragma unroll
-      for (int u = 0; u < RANK_U; ++u) {
-        const int i = base0 + 64 * u + lane;
-        key[u] = i < hi ? ksrc[i] : 0ull;
-      }
-#pragma unroll
-      for (int u = 0; u < RANK_U; ++u) {
-        if (base0 + 64 * u >= hi) break;
-        const bool valid = base0 + 64 * u + lane < hi;
-        const uint32_t dg = rank_digit(key[u], pass);
-        const uint64_t m = rank_match(dg, valid, nbits);
-        if (valid && (m & lt) == 0) hw[dg] += (uint32_t)__popcll(m);
-      }
-    }
-    __syncthreads();
-    {  // exclusive scan in (digit, wave) order; thread tid owns digit tid
-      uint32_t c[NW];
-      int s = 0;
-#pragma unroll
-      for (int i = 0; i < NW; ++i) {
-        c[i] = hist[i * tiles::R + tid];
-        s += (int)c[i];
-      }
-      int off = block_incl_scan(s, wtot) - s;
-#pragma unroll
-      for (int i = 0; i < NW; ++i) {
-        hist[i * tiles::R + tid] = (uint32_t)off;
-        off += (int)c[i];
-      }
-    }
-    __syncthreads();
-    for (int base0 = lo; base0 < hi; base0 += 64 * RANK_U) {
-      uint64_t key[RANK_U];
-      uint32_t card[RANK_U];
-#pragma unroll
-      for (int u = 0; u < RANK_U; ++u) {
-        const int i = base0 + 64 * u + lane;
-        key[u] = i < hi ? ksrc[i] : 0ull;
-        card[u] = (pass == 0 || i >= hi) ? (uint32_t)i : csrc[i];
-      }
-#pragma unroll
-      for (int u = 0; u < RANK_U; ++u) {
-        if (base0 + 64 * u >= hi) break;
-        const bool valid = base0 + 64 * u + lane < hi;
-        const uint32_t dg = rank_digit(key[u], pass);
-        const uint64_t m = rank_match(dg, valid, nbits);
-        const uint32_t basepos = hw[dg];
-        const uint32_t pos = basepos + (uint32_t)__popcll(m & lt);
-        if (valid && pos < (uint32_t)V) {  // pos >= V needs inconsistent counts: never write there
-          if (last) {
-            const int q = V - 1 - (int)pos;  // descending position
-            if (q < want) {
-              adds[q] = (int32_t)card[u];
-              if (addv) addv[q] = score_of(key[u]);
-            }
-          } else {
-            kdst[pos] = key[u];
-            cdst[pos] = card[u];
-          }
-        }
-        if (valid && (m & lt) == 0) hw[dg] = basepos + (uint32_t)__popcll(m);
-      }
-    }
-    __threadfence_block();
-    __syncthreads();
-  }
+  const int64_t o = (int64_t)r * Vp;
+  const GraphRankRow t{keys + (int64_t)r * Vs, ka + o, kb + o, ca + o, cb + o, adds, addv, V, want};
+  rowsort::radix_rank_row<SNT, RANK_U>(t, V, hist, wtot);
 }
 
 // workspace: the rows' sort keys [R][Vs]; Vs a multiple of 16, so rows start on a 128-byte line
@@ -495,9 +405,9 @@ struct RankWs {
 };
 RankWs rank_ws_of(void *base, int V, int R) {
   const size_t rows = (size_t)std::max(R, 1);
-  const size_t nk = tiles::align256(rows * key_pitch(V) * sizeof(uint64_t));
-  const size_t np8 = tiles::align256(rows * rank_pitch(V) * sizeof(uint64_t));
-  const size_t np4 = tiles::align256(rows * rank_pitch(V) * sizeof(uint32_t));
+  const size_t nk = align256(rows * key_pitch(V) * sizeof(uint64_t));
+  const size_t np8 = align256(rows * rank_pitch(V) * sizeof(uint64_t));
+  const size_t np4 = align256(rows * rank_pitch(V) * sizeof(uint32_t));
   char *p = (char *)base;
   RankWs w;
   w.keys = (uint64_t *)p;
@@ -549,7 +459,7 @@ extern "C" int32_t cc_graph_rec_max_amount(void) { return MAX_AMOUNT; }
 
 extern "C" size_t cc_graph_rec_ws_size(int32_t V, int32_t R, int32_t max_n) {
   (void)max_n;  // the cubes' ids are staged in LDS: nothing in the workspace scales with them
-  return tiles::align256((size_t)std::max(R, 1) * key_pitch(V) * sizeof(uint64_t)) + 256;
+  return align256((size_t)std::max(R, 1) * key_pitch(V) * sizeof(uint64_t)) + 256;
 }
 
 extern "C" int cc_graph_rec_f64(const double *adj, int64_t ld, int32_t V, int32_t R,

@@ -38,14 +38,8 @@ struct Tower {
   int d;
 };
 
-__device__ __forceinline__ float addf(float a, float b) {
-#pragma clang fp contract(off)
-  return a + b;
-}
-__device__ __forceinline__ float mulf(float a, float b) {
-#pragma clang fp contract(off)
-  return a * b;
-}
+using detm::addf;
+using detm::mulf;
 __device__ __forceinline__ float relu(float x) { return x > 0.f ? x : 0.f; }
 __device__ __forceinline__ float4 add4(float4 a, float4 b) {
   return make_float4(addf(a.x, b.x), addf(a.y, b.y), addf(a.z, b.z), addf(a.w, b.w));
@@ -328,7 +322,7 @@ int infer_h3_launch(const float *params, int V, int d, int R, const int32_t *row
 // ---------------------------------------------------------------------- single-cube request
 // ws layout: [partials gather_cap(V)*d floats][zlat 64][h3 d] | top-N sort workspace
 static size_t req_float_part(int V, int d) {
-  return tiles::align256(((size_t)gather_cap(V) * d + 64 + d) * sizeof(float));
+  return align256(((size_t)gather_cap(V) * d + 64 + d) * sizeof(float));
 }
 
 extern "C" size_t cc_recommend_ws_size(int32_t V, int32_t d) {

@@ -25,8 +25,9 @@
 //                     probabilities higher card index first; cube cards (key' = 0) never make it
 //                     because want <= V - n.
 // cc_recommend_batch_rank_fp32 runs the same chain for any amount, with the select replaced by
-//   rank_rows_kernel: one workgroup per row sorts all V (key', card) pairs (stable LSD radix
-//                     sort, three 10-bit passes through two ping-pong buffers in the workspace)
+//   rank_rows_kernel: one workgroup per row sorts all V (key', card) pairs (rowsort.hpp's stable
+//                     LSD radix sort, three 10-bit passes through two ping-pong buffers in the
+//                     workspace)
 //                     and writes the first want entries of the descending order.
 // cc_recommend_batch_target_ranks_fp32 runs the same chain and then, instead of ranking the row,
 //   target_ranks_kernel: one workgroup per row counts, for each of the row's chosen target cards,
@@ -40,6 +41,7 @@
 //                     n_cand[r] instead of V - n; target_ranks_kernel is fed the pooled keys.
 #include "common.hpp"
 #include "detmath.hpp"
+#include "rowsort.hpp"
 #include "topn_tiles.hpp"
 
 namespace cc {
@@ -61,14 +63,8 @@ constexpr int ONT = 256;     // output-tile workgroup: 16 card groups x 16 row g
 constexpr int SNT = 1024;    // top-N workgroup
 constexpr int MAX_AMOUNT = 2048;  // survivors sorted in LDS
 
-__device__ __forceinline__ float addf(float a, float b) {
-#pragma clang fp contract(off)
-  return a + b;
-}
-__device__ __forceinline__ float mulf(float a, float b) {
-#pragma clang fp contract(off)
-  return a * b;
-}
+using detm::addf;
+using detm::mulf;
 
 __global__ __launch_bounds__(256) void row_bits_kernel(const int32_t *__restrict__ row_ptr,
                                                        const int32_t *__restrict__ idx, int V,
@@ -248,45 +244,6 @@ __global__ __launch_bounds__(ONT) void out_tile_kernel(
   }
 }
 
-// Inclusive scan of one int per thread over the SNT-thread block; wtot: [SNT/64] LDS scratch.
-__device__ __forceinline__ int block_incl_scan(int v, int *wtot) {
-  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-  int x = v;
-#pragma unroll
-  for (int off = 1; off < 64; off <<= 1) {
-    const int y = __shfl_up(x, off, 64);
-    if (lane >= off) x += y;
-  }
-  if (lane == 63) wtot[w] = x;
-  __syncthreads();
-  int before = 0;
-#pragma unroll
-  for (int i = 0; i < SNT / 64; ++i) before += i < w ? wtot[i] : 0;
-  __syncthreads();
-  return before + x;
-}
-
-// Bitonic sort of a[0 .. P) in LDS, descending, by the whole SNT-thread block; P a power of two,
-// the entries written and a barrier passed before the call.  Every step ends with a barrier.
-__device__ __forceinline__ void bitonic_sort_desc(uint64_t *a, int P) {
-  const int tid = threadIdx.x;
-  for (int size = 2; size <= P; size <<= 1)
-    for (int stride = size >> 1; stride > 0; stride >>= 1) {
-      for (int i = tid; i < P; i += SNT) {
-        const int pr = i ^ stride;
-        if (pr > i) {
-          const bool down = (i & size) == 0;
-          const uint64_t x = a[i], y = a[pr];
-          if ((x < y) == down) {
-            a[i] = y;
-            a[pr] = x;
-          }
-        }
-      }
-      __syncthreads();
-    }
-}
-
 // POOL: the row's candidates are the n_cand[r] cards whose exclusion bit is clear (row_mask_kernel),
 // and every other card has key' = 0: want <= n_cand[r], so the want-th largest composite is a
 // candidate's, the select's threshold has key' != 0 and no excluded card passes it.
@@ -341,7 +298,7 @@ __global__ __launch_bounds__(SNT) void topn_rows_kernel(const uint32_t *__restri
     __syncthreads();
     // thread t owns bin 1023 - t: its inclusive scan is the count of matching items in bins >= it
     const int v = (int)hist[1023 - tid];
-    const int ge = block_incl_scan(v, wtot), gt = ge - v;
+    const int ge = rowsort::block_incl_scan<SNT>(v, wtot), gt = ge - v;
     if (ge >= rem && gt < rem) {  // exactly one bin: the one holding the rem-th largest
       s_prefix = prefix | ((uint64_t)(1023 - tid) << shift);
       s_mask = mask | ((uint64_t)dmask << shift);
@@ -363,7 +320,7 @@ __global__ __launch_bounds__(SNT) void topn_rows_kernel(const uint32_t *__restri
   while (P < want) P <<= 1;
   for (int i = min(s_cnt, want) + tid; i < P; i += SNT) sel[i] = 0ull;  // below every candidate
   __syncthreads();
-  bitonic_sort_desc(sel, P);
+  rowsort::bitonic_sort<SNT>(P, rowsort::CmpSwapU64<true>{sel});
   for (int i = tid; i < want; i += SNT) {
     const uint64_t cmp = sel[i];
     adds[i] = (int32_t)(uint32_t)cmp;
@@ -371,32 +328,42 @@ __global__ __launch_bounds__(SNT) void topn_rows_kernel(const uint32_t *__restri
   }
 }
 
-// Full ranking of one row: a stable LSD radix sort of ascending key' from ascending card order,
-// tiles::PASSES passes of tiles::BITS bits, one workgroup per row.  Wave w owns a contiguous slice
-// of the current arrangement; inside a wave the rank is a ballot multisplit, across waves the
-// exclusive scan of the (digit, wave) counts in digit-major order.  (key', card) pairs ping-pong
+// Full ranking of one row: rowsort::radix_rank_row over ascending key' from ascending card order,
+// tiles::PASSES passes of tiles::BITS bits, one workgroup per row.  (key', card) pairs ping-pong
 // through pa / pb as one 64-bit word; the last pass stores nothing but the row's results:
 // ascending position pos is descending position V - 1 - pos, and the cube cards (key' = 0) hold
 // the first n ascending positions, i.e. the last n descending ones, which want <= V - n never
 // reaches.  POOL: the excluded cards (cube or outside the pool, key' = 0) hold the first
 // V - n_cand[r] ascending positions, the last V - n_cand[r] descending ones, which
 // want <= n_cand[r] never reaches.
-__device__ __forceinline__ uint64_t rank_load(const uint32_t *k, const uint64_t *src, int pass,
-                                               int i) {
-  return pass == 0 ? ((uint64_t)k[i] << 32) | (uint32_t)i : src[i];
-}
-// the valid lanes of the wave that hold digit dg (a value below 2^nbits)
-__device__ __forceinline__ uint64_t rank_match(uint32_t dg, bool valid, int nbits = tiles::BITS) {
-  uint64_t m = __ballot(valid);
-#pragma unroll
-  for (int bit = 0; bit < nbits; ++bit) {
-    const bool b = (dg >> bit) & 1u;
-    const uint64_t bb = __ballot(b);
-    m &= b ? bb : ~bb;
-  }
-  return m;
-}
 constexpr int RU = 8;  // items a lane loads ahead of ranking them: the loads' latency is paid once
+
+struct RankRow {
+  using Item = uint64_t;  // key' << 32 | card
+  static constexpr int PASSES = tiles::PASSES, RADIX_BITS = tiles::BITS;
+  static __device__ constexpr int bits(int) { return tiles::BITS; }
+  const uint32_t *k;
+  uint64_t *bufa, *bufb;
+  int32_t *adds;
+  float *addv;
+  int V, want;
+  __device__ __forceinline__ Item load(int pass, int i) const {  // pass 0 reads the keys
+    return pass == 0 ? ((uint64_t)k[i] << 32) | (uint32_t)i : ((pass & 1) ? bufa : bufb)[i];
+  }
+  __device__ __forceinline__ uint32_t digit(Item x, int pass) const {
+    return tiles::digit((uint32_t)(x >> 32), pass);
+  }
+  __device__ __forceinline__ void store(int pass, uint32_t pos, Item x) const {
+    ((pass & 1) ? bufb : bufa)[pos] = x;
+  }
+  __device__ __forceinline__ void emit(uint32_t pos, Item x) const {
+    const int q = V - 1 - (int)pos;  // descending position
+    if (q < want) {
+      adds[q] = (int32_t)(uint32_t)x;
+      addv[q] = __uint_as_float((uint32_t)(x >> 32) - 1u);
+    }
+  }
+};
 
 template <bool POOL>
 __global__ __launch_bounds__(SNT) void rank_rows_kernel(const uint32_t *__restrict__ keys, int Vs,
@@ -407,11 +374,9 @@ __global__ __launch_bounds__(SNT) void rank_rows_kernel(const uint32_t *__restri
                                                         int32_t *__restrict__ additions,
                                                         float *__restrict__ add_vals,
                                                         const int32_t *__restrict__ n_cand) {
-  constexpr int NW = SNT / 64;
-  __shared__ uint32_t hist[NW * tiles::R];  // [wave][digit]: a thread scans its digit's column
-  __shared__ int wtot[NW];
-  const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
-  const uint64_t lt = (1ull << lane) - 1ull;
+  __shared__ uint32_t hist[SNT / 64 * tiles::R];
+  __shared__ int wtot[SNT / 64];
+  const int tid = threadIdx.x;
   const int r = blockIdx.x;
   const int cand = POOL ? n_cand[r] : V - (row_ptr[r + 1] - row_ptr[r]);
   const int want = max(0, min(amount > 0 ? amount : 1, cand));
@@ -423,84 +388,8 @@ __global__ __launch_bounds__(SNT) void rank_rows_kernel(const uint32_t *__restri
   }
   if (tid == 0) n_add[r] = want;
   if (want == 0) return;
-  const uint32_t *k = keys + (int64_t)r * Vs;
-  uint64_t *bufa = pa + (int64_t)r * Vp, *bufb = pb + (int64_t)r * Vp;
-  const int S = (int)cdiv(cdiv(V, NW), 64) * 64;  // per-wave slice
-  const int lo = w * S, hi = min(V, lo + S);
-  uint32_t *hw = hist + w * tiles::R;
-  for (int pass = 0; pass < tiles::PASSES; ++pass) {
-    const uint64_t *src = (pass & 1) ? bufa : bufb;  // pass 0 reads the keys instead
-    uint64_t *dst = (pass & 1) ? bufb : bufa;
-    const bool last = pass == tiles::PASSES - 1;
-#pragma unroll
-    for (int i = 0; i < NW; ++i) hist[i * tiles::R + tid] = 0u;
-    __syncthreads();
-    for (int base0 = lo; base0 < hi; base0 += 64 * RU) {
-      uint64_t item[RU];
-#pragma unroll
-      for (int u = 0; u < RU; ++u) {
-        const int i = base0 + 64 * u + lane;
-        item[u] = i < hi ? rank_load(k, src, pass, i) : 0ull;
-      }
-#pragma unroll
-      for (int u = 0; u < RU; ++u) {
-        if (base0 + 64 * u >= hi) break;
-        const bool valid = base0 + 64 * u + lane < hi;
-        const uint32_t dg = tiles::digit((uint32_t)(item[u] >> 32), pass);
-        const uint64_t m = rank_match(dg, valid);
-        if (valid && (m & lt) == 0) hw[dg] += (uint32_t)__popcll(m);
-      }
-    }
-    __syncthreads();
-    {  // exclusive scan in (digit, wave) order; thread tid owns digit tid
-      uint32_t c[NW];
-      int s = 0;
-#pragma unroll
-      for (int i = 0; i < NW; ++i) {
-        c[i] = hist[i * tiles::R + tid];
-        s += (int)c[i];
-      }
-      int off = block_incl_scan(s, wtot) - s;
-#pragma unroll
-      for (int i = 0; i < NW; ++i) {
-        hist[i * tiles::R + tid] = (uint32_t)off;
-        off += (int)c[i];
-      }
-    }
-    __syncthreads();
-    for (int base0 = lo; base0 < hi; base0 += 64 * RU) {
-      uint64_t item[RU];
-#pragma unroll
-      for (int u = 0; u < RU; ++u) {
-        const int i = base0 + 64 * u + lane;
-        item[u] = i < hi ? rank_load(k, src, pass, i) : 0ull;
-      }
-#pragma unroll
-      for (int u = 0; u < RU; ++u) {
-        if (base0 + 64 * u >= hi) break;
-        const bool valid = base0 + 64 * u + lane < hi;
-        const uint32_t key = (uint32_t)(item[u] >> 32);
-        const uint32_t dg = tiles::digit(key, pass);
-        const uint64_t m = rank_match(dg, valid);
-        const uint32_t basepos = hw[dg];
-        const uint32_t pos = basepos + (uint32_t)__popcll(m & lt);
-        if (valid && pos < (uint32_t)V) {  // pos >= V needs inconsistent counts: never write there
-          if (last) {
-            const int q = V - 1 - (int)pos;  // descending position
-            if (q < want) {
-              adds[q] = (int32_t)(uint32_t)item[u];
-              addv[q] = __uint_as_float(key - 1u);
-            }
-          } else {
-            dst[pos] = item[u];
-          }
-        }
-        if (valid && (m & lt) == 0) hw[dg] = basepos + (uint32_t)__popcll(m);
-      }
-    }
-    __threadfence_block();
-    __syncthreads();
-  }
+  const RankRow t{keys + (int64_t)r * Vs, pa + (int64_t)r * Vp, pb + (int64_t)r * Vp, adds, addv, V, want};
+  rowsort::radix_rank_row<SNT, RU>(t, V, hist, wtot);
 }
 
 // Position of chosen cards in a row's ranking without sorting the row: the rank of target t is the
@@ -567,7 +456,7 @@ __global__ __launch_bounds__(SNT) __attribute__((amdgpu_waves_per_eu(8, 8))) voi
       cnt[i] = 0u;
     }
     __syncthreads();
-    bitonic_sort_desc(srt, P);
+    rowsort::bitonic_sort<SNT>(P, rowsort::CmpSwapU64<true>{srt});
     int Tv = 0;  // valid targets: the first position holding 0
     for (int hi = P; Tv < hi;) {
       const int mid = (Tv + hi) >> 1;
@@ -591,7 +480,7 @@ __global__ __launch_bounds__(SNT) __attribute__((amdgpu_waves_per_eu(8, 8))) voi
               const int mid = (g + hi) >> 1;
               if (srt[mid] >= x) g = mid + 1; else hi = mid;
             }
-          const uint64_t m = rank_match((uint32_t)g, above, nbits);
+          const uint64_t m = rowsort::wave_match((uint32_t)g, above, nbits);
           if (above && (m & lt) == 0ull) atomicAdd(&cnt[g], (uint32_t)__popcll(m));
         }
       }
@@ -600,7 +489,7 @@ __global__ __launch_bounds__(SNT) __attribute__((amdgpu_waves_per_eu(8, 8))) voi
     {  // inclusive prefix sums in place; thread tid owns counters 2 tid and 2 tid + 1
       const int c0 = 2 * tid < P ? (int)cnt[2 * tid] : 0;
       const int c1 = 2 * tid + 1 < P ? (int)cnt[2 * tid + 1] : 0;
-      const int incl = block_incl_scan(c0 + c1, wtot);
+      const int incl = rowsort::block_incl_scan<SNT>(c0 + c1, wtot);
       if (2 * tid < P) cnt[2 * tid] = (uint32_t)(incl - c1);
       if (2 * tid + 1 < P) cnt[2 * tid + 1] = (uint32_t)incl;
     }
@@ -668,11 +557,11 @@ BatchWs batch_ws(int V, int d, int R, int max_n) {
   w.Vs = (std::max(V, 1) + 3) & ~3;
   w.VW = (std::max(V, 1) + 31) / 32;
   size_t o = 0;
-  w.part = o, o += tiles::align256(r * cc::infer_gather_cap(max_n) * dd * sizeof(float));
-  w.zlat = o, o += tiles::align256(r * 64 * sizeof(float));
-  w.h3 = o, o += tiles::align256(r * dd * sizeof(float));
-  w.keys = o, o += tiles::align256(r * w.Vs * sizeof(uint32_t));
-  w.bits = o, o += tiles::align256(r * w.VW * sizeof(uint32_t));
+  w.part = o, o += align256(r * cc::infer_gather_cap(max_n) * dd * sizeof(float));
+  w.zlat = o, o += align256(r * 64 * sizeof(float));
+  w.h3 = o, o += align256(r * dd * sizeof(float));
+  w.keys = o, o += align256(r * w.Vs * sizeof(uint32_t));
+  w.bits = o, o += align256(r * w.VW * sizeof(uint32_t));
   w.total = o;
   return w;
 }
@@ -686,8 +575,8 @@ PoolWs pool_ws(const BatchWs &w, int R) {
   PoolWs p;
   const size_t r = (size_t)std::max(R, 1);
   size_t o = w.total;
-  p.excl = o, o += tiles::align256(r * w.VW * sizeof(uint32_t));
-  p.ncand = o, o += tiles::align256(r * sizeof(int32_t));
+  p.excl = o, o += align256(r * w.VW * sizeof(uint32_t));
+  p.ncand = o, o += align256(r * sizeof(int32_t));
   p.total = o;
   return p;
 }
@@ -837,7 +726,7 @@ extern "C" int cc_recommend_batch_pool_fp32(const float *params, int32_t V, int3
 // 64-bit words; Vp is a multiple of 16, so no two rows share a 128-byte line
 static size_t rank_pitch(int V) { return ((size_t)std::max(V, 1) + 15) & ~(size_t)15; }
 static size_t rank_buf_bytes(int V, int R) {
-  return tiles::align256((size_t)std::max(R, 1) * rank_pitch(V) * sizeof(uint64_t));
+  return align256((size_t)std::max(R, 1) * rank_pitch(V) * sizeof(uint64_t));
 }
 
 extern "C" size_t cc_recommend_batch_rank_ws_size(int32_t V, int32_t d, int32_t R, int32_t max_n) {

@@ -34,6 +34,8 @@
 #include <algorithm>
 
 #include "common.hpp"
+#include "detmath.hpp"
+#include "rowsort.hpp"
 
 namespace {
 
@@ -45,23 +47,11 @@ constexpr int SNT = 1024;     // select / sort workgroup
 constexpr int MAX_N = 2048;   // survivors sorted in LDS
 constexpr int MAX_Q = 1 << 22;
 constexpr int SBITS = 8;      // sort digit
-constexpr int SR = 1 << SBITS;
 constexpr int SPASSES = 4;
 
-__device__ __forceinline__ float addf(float a, float b) {
-#pragma clang fp contract(off)
-  return a + b;
-}
-__device__ __forceinline__ float mulf(float a, float b) {
-#pragma clang fp contract(off)
-  return a * b;
-}
-
-// similarity.hip's sort key: ascending key == ascending float, -0 folded into +0
-__device__ __forceinline__ uint32_t orderable(float f) {
-  uint32_t u = __float_as_uint(f == 0.f ? 0.f : f);
-  return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-}
+using detm::addf;
+using detm::mulf;
+using rowsort::orderable;  // similarity.hip's sort key
 // its inverse on distances: the only zero a distance takes is -0.0f
 __device__ __forceinline__ float dist_of_key(uint32_t key) {
   if (key == 0x80000000u) return __uint_as_float(0x80000000u);
@@ -216,24 +206,6 @@ __global__ __launch_bounds__(DNT) void dist_tile_kernel(const float *__restrict_
   }
 }
 
-// Inclusive scan of one int per thread over the SNT-thread block; wtot: [SNT/64] LDS scratch.
-__device__ __forceinline__ int block_incl_scan(int v, int *wtot) {
-  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-  int x = v;
-#pragma unroll
-  for (int off = 1; off < 64; off <<= 1) {
-    const int y = __shfl_up(x, off, 64);
-    if (lane >= off) x += y;
-  }
-  if (lane == 63) wtot[w] = x;
-  __syncthreads();
-  int before = 0;
-#pragma unroll
-  for (int i = 0; i < SNT / 64; ++i) before += i < w ? wtot[i] : 0;
-  __syncthreads();
-  return before + x;
-}
-
 // A row whose query id is outside [0, V): -1 / 0.f, nothing read.
 __device__ __forceinline__ void fill_invalid_row(int32_t *oi, float *od, int N) {
   for (int i = threadIdx.x; i < N; i += SNT) {
@@ -293,7 +265,7 @@ __global__ __launch_bounds__(SNT) void select_rows_kernel(const uint32_t *__rest
     __syncthreads();
     // thread t owns bin t: its inclusive scan is the count of matching items in bins <= it
     const int v = (int)hist[tid];
-    const int le = block_incl_scan(v, wtot), lt = le - v;
+    const int le = rowsort::block_incl_scan<SNT>(v, wtot), lt = le - v;
     if (le >= rem && lt < rem) {  // exactly one bin: the one holding the rem-th smallest
       s_prefix = prefix | ((uint64_t)tid << shift);
       s_mask = mask | ((uint64_t)dmask << shift);
@@ -318,21 +290,7 @@ __global__ __launch_bounds__(SNT) void select_rows_kernel(const uint32_t *__rest
   while (P < cnt) P <<= 1;
   for (int i = cnt + tid; i < P; i += SNT) sel[i] = ~0ull;  // above every candidate
   __syncthreads();
-  for (int size = 2; size <= P; size <<= 1)
-    for (int stride = size >> 1; stride > 0; stride >>= 1) {
-      for (int i = tid; i < P; i += SNT) {
-        const int pr = i ^ stride;
-        if (pr > i) {
-          const bool up = (i & size) == 0;
-          const uint64_t a = sel[i], b = sel[pr];
-          if ((a > b) == up) {
-            sel[i] = b;
-            sel[pr] = a;
-          }
-        }
-      }
-      __syncthreads();
-    }
+  rowsort::bitonic_sort<SNT>(P, rowsort::CmpSwapU64<false>{sel});
   for (int i = tid; i < N; i += SNT) {
     const uint64_t cmp = sel[i];
     oi[i] = (int32_t)(uint32_t)cmp;
@@ -340,41 +298,45 @@ __global__ __launch_bounds__(SNT) void select_rows_kernel(const uint32_t *__rest
   }
 }
 
-// Full ranking of one row (recbatch.hip's rank_rows_kernel with a digit plan for 32-bit keys and
-// the ascending order kept): wave w owns a contiguous slice of the current arrangement; inside a
-// wave the rank is a ballot multisplit, across waves the exclusive scan of the (digit, wave)
-// counts in digit-major order.  (key, card) pairs ping-pong through pa / pb as one 64-bit word;
-// the last pass stores nothing but the row's first N.
-__device__ __forceinline__ uint64_t sort_load(const uint32_t *k, const uint64_t *src, int pass, int i) {
-  return pass == 0 ? ((uint64_t)k[i] << 32) | (uint32_t)i : src[i];
-}
-__device__ __forceinline__ uint32_t sort_digit(uint32_t key, int pass) {
-  return (key >> (SBITS * pass)) & (uint32_t)(SR - 1);
-}
-// the valid lanes of the wave that hold digit dg
-__device__ __forceinline__ uint64_t sort_match(uint32_t dg, bool valid) {
-  uint64_t m = __ballot(valid);
-#pragma unroll
-  for (int bit = 0; bit < SBITS; ++bit) {
-    const bool b = (dg >> bit) & 1u;
-    const uint64_t bb = __ballot(b);
-    m &= b ? bb : ~bb;
-  }
-  return m;
-}
+// Full ranking of one row: rowsort::radix_rank_row with a digit plan for 32-bit keys (a distance key
+// differs in all 32 bits) and the ascending order kept.  (key, card) pairs ping-pong through
+// pa / pb as one 64-bit word; the last pass stores nothing but the row's first N.
 constexpr int RU = 8;  // items a lane loads ahead of ranking them
+
+struct SortRow {
+  using Item = uint64_t;  // key << 32 | card
+  static constexpr int PASSES = SPASSES, RADIX_BITS = SBITS;
+  static_assert(SPASSES % 2 == 0 && SBITS * SPASSES == 32, "pass 0 reads the keys, the last writes the results");
+  static __device__ constexpr int bits(int) { return SBITS; }
+  const uint32_t *k;
+  uint64_t *bufa, *bufb;
+  int32_t *oi;
+  float *od;
+  int N;
+  __device__ __forceinline__ Item load(int pass, int i) const {  // pass 0 reads the keys
+    return pass == 0 ? ((uint64_t)k[i] << 32) | (uint32_t)i : ((pass & 1) ? bufa : bufb)[i];
+  }
+  __device__ __forceinline__ uint32_t digit(Item x, int pass) const {
+    return ((uint32_t)(x >> 32) >> (SBITS * pass)) & (uint32_t)((1 << SBITS) - 1);
+  }
+  __device__ __forceinline__ void store(int pass, uint32_t pos, Item x) const {
+    ((pass & 1) ? bufb : bufa)[pos] = x;
+  }
+  __device__ __forceinline__ void emit(uint32_t pos, Item x) const {
+    if (pos < (uint32_t)N) {
+      oi[pos] = (int32_t)(uint32_t)x;
+      od[pos] = dist_of_key((uint32_t)(x >> 32));
+    }
+  }
+};
 
 __global__ __launch_bounds__(SNT) void sort_rows_kernel(const uint32_t *__restrict__ keys, int Vs,
                                                         int V, const int32_t *__restrict__ queries,
                                                         int N, uint64_t *pa, uint64_t *pb, int Vp,
                                                         int32_t *__restrict__ out_idx,
                                                         float *__restrict__ out_dist) {
-  constexpr int NW = SNT / 64;
-  static_assert(SPASSES % 2 == 0 && SBITS * SPASSES == 32, "pass 0 reads the keys, the last writes the results");
-  __shared__ uint32_t hist[NW * SR];  // [wave][digit]: a thread scans its digit's column
-  __shared__ int wtot[NW];
-  const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
-  const uint64_t lt = (1ull << lane) - 1ull;
+  __shared__ uint32_t hist[SNT / 64 << SBITS];
+  __shared__ int wtot[SNT / 64];
   const int r = blockIdx.x;
   int32_t *oi = out_idx + (int64_t)r * N;
   float *od = out_dist + (int64_t)r * N;
@@ -382,89 +344,9 @@ __global__ __launch_bounds__(SNT) void sort_rows_kernel(const uint32_t *__restri
     fill_invalid_row(oi, od, N);
     return;
   }
-  const uint32_t *k = keys + (int64_t)r * Vs;
-  uint64_t *bufa = pa + (int64_t)r * Vp, *bufb = pb + (int64_t)r * Vp;
-  const int S = (int)cdiv(cdiv(V, NW), 64) * 64;  // per-wave slice
-  const int lo = min(V, w * S), hi = min(V, lo + S);
-  uint32_t *hw = hist + w * SR;
-  for (int pass = 0; pass < SPASSES; ++pass) {
-    const uint64_t *src = (pass & 1) ? bufa : bufb;  // pass 0 reads the keys instead
-    uint64_t *dst = (pass & 1) ? bufb : bufa;
-    const bool last = pass == SPASSES - 1;
-    for (int i = tid; i < NW * SR; i += SNT) hist[i] = 0u;
-    __syncthreads();
-    for (int base0 = lo; base0 < hi; base0 += 64 * RU) {
-      uint64_t item[RU];
-#pragma unroll
-      for (int u = 0; u < RU; ++u) {
-        const int i = base0 + 64 * u + lane;
-        item[u] = i < hi ? sort_load(k, src, pass, i) : 0ull;
-      }
-#pragma unroll
-      for (int u = 0; u < RU; ++u) {
-        if (base0 + 64 * u >= hi) break;
-        const bool valid = base0 + 64 * u + lane < hi;
-        const uint32_t dg = sort_digit((uint32_t)(item[u] >> 32), pass);
-        const uint64_t m = sort_match(dg, valid);
-        if (valid && (m & lt) == 0) hw[dg] += (uint32_t)__popcll(m);
-      }
-    }
-    __syncthreads();
-    {  // exclusive scan in (digit, wave) order; thread tid < SR owns digit tid
-      uint32_t c[NW];
-      int s = 0;
-      if (tid < SR) {
-#pragma unroll
-        for (int i = 0; i < NW; ++i) {
-          c[i] = hist[i * SR + tid];
-          s += (int)c[i];
-        }
-      }
-      int off = block_incl_scan(s, wtot) - s;
-      if (tid < SR) {
-#pragma unroll
-        for (int i = 0; i < NW; ++i) {
-          hist[i * SR + tid] = (uint32_t)off;
-          off += (int)c[i];
-        }
-      }
-    }
-    __syncthreads();
-    for (int base0 = lo; base0 < hi; base0 += 64 * RU) {
-      uint64_t item[RU];
-#pragma unroll
-      for (int u = 0; u < RU; ++u) {
-        const int i = base0 + 64 * u + lane;
-        item[u] = i < hi ? sort_load(k, src, pass, i) : 0ull;
-      }
-#pragma unroll
-      for (int u = 0; u < RU; ++u) {
-        if (base0 + 64 * u >= hi) break;
-        const bool valid = base0 + 64 * u + lane < hi;
-        const uint32_t key = (uint32_t)(item[u] >> 32);
-        const uint32_t dg = sort_digit(key, pass);
-        const uint64_t m = sort_match(dg, valid);
-        const uint32_t basepos = hw[dg];
-        const uint32_t pos = basepos + (uint32_t)__popcll(m & lt);
-        if (valid && pos < (uint32_t)V) {  // pos >= V needs inconsistent counts: never write there
-          if (last) {
-            if (pos < (uint32_t)N) {
-              oi[pos] = (int32_t)(uint32_t)item[u];
-              od[pos] = dist_of_key(key);
-            }
-          } else {
-            dst[pos] = item[u];
-          }
-        }
-        if (valid && (m & lt) == 0) hw[dg] = basepos + (uint32_t)__popcll(m);
-      }
-    }
-    __threadfence_block();
-    __syncthreads();
-  }
+  const SortRow t{keys + (int64_t)r * Vs, pa + (int64_t)r * Vp, pb + (int64_t)r * Vp, oi, od, N};
+  rowsort::radix_rank_row<SNT, RU>(t, V, hist, wtot);
 }
-
-inline size_t align256(size_t x) { return (x + 255) & ~(size_t)255; }
 
 // workspace: [n V*Kp][nT Kp*Vs][keys Q*Vs] and, for N above the select's cap, the two
 // (key, card) ping-pong buffers [Q][Vp] of 64-bit words (Vp a multiple of 16: no two rows share a

@@ -15,16 +15,14 @@
 //                        64-bit key over all V keys (8 passes of LDS histograms), then the <= N
 //                        selected keys bitonic-sorted in LDS.  Keys are unique, so exactly N.
 #include "common.hpp"
+#include "rowsort.hpp"
 
 namespace {
 
 constexpr int SIM_NT = 1024;
 constexpr int SIM_NMAX = 4096;  // N <= 4096 (the LDS sort)
 
-__device__ __forceinline__ uint32_t orderable(float f) {
-  uint32_t u = __float_as_uint(f == 0.f ? 0.f : f);  // -0 == +0 for the ranking
-  return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-}
+using rowsort::orderable;  // -0 == +0 for the ranking
 
 __global__ __launch_bounds__(256) void cosine_dist_kernel(const float *__restrict__ emb, int V, int K,
                                                           int q, float *__restrict__ dist,
@@ -90,21 +88,7 @@ __global__ __launch_bounds__(SIM_NT) void rank_smallest_kernel(const uint64_t *_
   while (P < N) P <<= 1;
   for (int i = N + tid; i < P; i += SIM_NT) sel[i] = ~0ull;
   __syncthreads();
-  for (int size = 2; size <= P; size <<= 1)
-    for (int stride = size >> 1; stride > 0; stride >>= 1) {
-      for (int i = tid; i < P; i += SIM_NT) {
-        const int pr = i ^ stride;
-        if (pr > i) {
-          const bool up = (i & size) == 0;
-          const uint64_t a = sel[i], b = sel[pr];
-          if ((a > b) == up) {
-            sel[i] = b;
-            sel[pr] = a;
-          }
-        }
-      }
-      __syncthreads();
-    }
+  rowsort::bitonic_sort<SIM_NT>(P, rowsort::CmpSwapU64<false>{sel});
   for (int i = tid; i < N; i += SIM_NT) {
     const int j = (int)(uint32_t)sel[i];
     out_idx[i] = j;

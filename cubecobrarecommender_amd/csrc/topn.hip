@@ -21,6 +21,7 @@
 // Full ranking (`order` != NULL; tests and tools): one 1024-thread workgroup runs the same
 // stable sort with keys/ids ping-ponging through the global workspace (topn_full_kernel).
 #include "common.hpp"
+#include "rowsort.hpp"
 #include "topn_tiles.hpp"
 
 namespace {
@@ -29,55 +30,7 @@ constexpr int FNT = 1024;  // full-ranking workgroup
 constexpr int FNW = FNT / 64;
 constexpr int RADIX = 256;
 
-__device__ __forceinline__ uint64_t match_digit(uint32_t dgt, bool valid) {
-  uint64_t m = __ballot(valid);
-#pragma unroll
-  for (int bit = 0; bit < 8; ++bit) {
-    const bool b = (dgt >> bit) & 1u;
-    const uint64_t bb = __ballot(b);
-    m &= b ? bb : ~bb;
-  }
-  return m;
-}
-
-// Exclusive scan over the block of one int per thread; wtot: [blockDim/64] LDS scratch.
-template <int THREADS>
-__device__ __forceinline__ int block_excl_scan2(int v, int *wtot, int *total) {
-  constexpr int W = THREADS / 64;
-  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-  int x = v;
-#pragma unroll
-  for (int off = 1; off < 64; off <<= 1) {
-    const int y = __shfl_up(x, off, 64);
-    if (lane >= off) x += y;
-  }
-  if (lane == 63) wtot[w] = x;
-  __syncthreads();
-  int before = 0, all = 0;
-#pragma unroll
-  for (int i = 0; i < W; ++i) {
-    const int t = wtot[i];
-    before += i < w ? t : 0;
-    all += t;
-  }
-  __syncthreads();
-  if (total) *total = all;
-  return before + x - v;
-}
-
 // ------------------------------------------------------------------ tiled request path
-template <int BITS>
-__device__ __forceinline__ uint64_t match_bits(uint32_t dgt, bool valid) {
-  uint64_t m = __ballot(valid);
-#pragma unroll
-  for (int bit = 0; bit < BITS; ++bit) {
-    const bool b = (dgt >> bit) & 1u;
-    const uint64_t bb = __ballot(b);
-    m &= b ? bb : ~bb;
-  }
-  return m;
-}
-
 // cc_topn entry: keys/ids of tile t, its pass-0 histogram; H[1..] zeroed.
 __global__ __launch_bounds__(tiles::NT) void topn_init_kernel(const float *__restrict__ probs,
                                                               int V, const int32_t *__restrict__ cube_idx,
@@ -158,7 +111,7 @@ __global__ __launch_bounds__(tiles::NT) void topn_pass_kernel(int pass, int V, i
   for (int it = 0; it < IT; ++it) {
     const bool valid = base + it * 64 < V;
     const uint32_t d = digit(key[it], pass);
-    const uint64_t m = match_bits<BITS>(d, valid);
+    const uint64_t m = rowsort::wave_match<BITS>(d, valid);
     const uint32_t r = valid ? wcnt[wv][d] : 0u;
     rk[it] = r + (uint32_t)__popcll(m & lt);
     if (valid && (m & lt) == 0) wcnt[wv][d] = r + (uint32_t)__popcll(m);
@@ -188,7 +141,7 @@ __global__ __launch_bounds__(tiles::NT) void topn_pass_kernel(int pass, int V, i
     int sum = 0;
 #pragma unroll
     for (int j = 0; j < PER; ++j) sum += tot[j];
-    int off = block_excl_scan2<NT>(sum, wtot, nullptr);  // synchronises the block
+    int off = rowsort::block_incl_scan<NT>(sum, wtot) - sum;  // synchronises the block
 #pragma unroll
     for (int j = 0; j < PER; ++j) {
       gbase[PER * threadIdx.x + j] = (uint32_t)(off + before[j]);
@@ -255,7 +208,7 @@ __device__ __forceinline__ void scan_hist(uint32_t *hist, int *wtot) {
     loc[e] = hist[threadIdx.x * PER + e];
     s += (int)loc[e];
   }
-  int off = block_excl_scan2<FNT>(s, wtot, nullptr);
+  int off = rowsort::block_incl_scan<FNT>(s, wtot) - s;
 #pragma unroll
   for (int e = 0; e < PER; ++e) {
     hist[threadIdx.x * PER + e] = (uint32_t)off;
@@ -319,7 +272,7 @@ __global__ __launch_bounds__(FNT) void topn_full_kernel(const float *__restrict_
       uint32_t key = 0;
       if (valid) key = pass == 0 ? __float_as_uint(probs[i]) : ksrc[i];
       const uint32_t dg = (key >> shift) & 0xFFu;
-      const uint64_t m = match_digit(dg, valid);
+      const uint64_t m = rowsort::wave_match<8>(dg, valid);
       if (valid && (m & lt) == 0) hist[dg * FNW + w] += (uint32_t)__popcll(m);
     }
     __syncthreads();
@@ -335,7 +288,7 @@ __global__ __launch_bounds__(FNT) void topn_full_kernel(const float *__restrict_
         val = pass == 0 ? i : vsrc[i];
       }
       const uint32_t dg = (key >> shift) & 0xFFu;
-      const uint64_t m = match_digit(dg, valid);
+      const uint64_t m = rowsort::wave_match<8>(dg, valid);
       uint32_t basepos = 0;
       if (valid) basepos = hist[dg * FNW + w];
       if (valid) {

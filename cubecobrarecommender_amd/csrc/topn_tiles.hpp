@@ -29,7 +29,6 @@ __device__ __forceinline__ uint32_t key_of(float p, bool in_cube) {
 struct Ws {
   uint32_t *kA, *iA, *kB, *iB, *H, *bits;
 };
-__host__ __device__ inline size_t align256(size_t x) { return (x + 255) & ~(size_t)255; }
 __host__ __device__ inline Ws ws_of(void *base, int V) {
   char *p = (char *)base;
   const size_t v = align256((size_t)V * 4);

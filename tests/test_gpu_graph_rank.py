@@ -114,6 +114,41 @@ def test_direct_call(V, pad):
         check_rows(out, V, cubes, want, full, V, vals=False)
 
 
+def test_slices_longer_than_one_load_ahead():
+    """V = 8257: a wave's slice of the sort is 576 items, more than the 64 * 8 a wave loads ahead
+    of ranking them, so the load-ahead loop runs a second, partly filled iteration; wave 14 holds
+    193 items and wave 15 none.  The matrix is zero except the rows and columns of the cards the
+    three cubes name ('wild' values: every entry a score can read), and in those rows every third
+    column is zero again: a third of the cards tie at +0.0 in every row, across every slice edge."""
+    V, waves, ahead = 8257, 16, 64 * 8
+    S = ((V + waves - 1) // waves + 63) // 64 * 64                         # the kernel's per-wave slice
+    assert S == 576 and ahead < S < 2 * ahead and 0 < V - 14 * S < S and 15 * S >= V
+    rng = np.random.default_rng(8257)
+    edges = np.array([0, S - 1, S, S + ahead - 1, S + ahead, 14 * S - 1, 14 * S, V - 1])
+    cubes = [np.array([S]), edges, np.unique(np.concatenate([edges, rng.choice(V, 300, replace=False)]))]
+    named = np.unique(np.concatenate(cubes))
+    M = np.zeros((V, V))
+    wild = lambda shape: rng.normal(size=shape) * np.exp2(rng.uniform(-40, 40, size=shape))
+    M[named, :] = wild((len(named), V))
+    M[:, named] = wild((V, len(named)))
+    ties = np.setdiff1d(np.arange(0, V, 3), named)
+    M[np.ix_(named, ties)] = 0.0
+    want = [G.scores(M, c) for c in cubes]
+    full = [G.additions(s, c, V) for s, c in zip(want, cubes)]
+    for (order, vals), s in zip(full, want):
+        assert np.array_equal(bits(s[ties]), bits(np.zeros(len(ties))))
+        at = np.flatnonzero(vals == 0.0)                                    # one run, by descending card
+        assert len(at) >= len(ties) > V // 4 and np.all(np.diff(at) == 1) and np.all(np.diff(order[at]) < 0)
+        assert 0 < at[0] and at[-1] < len(vals) - 1
+    buf, ld = device_matrix(M, 0)
+    del M
+    for amount in (V, 2 ** 31 - 1):
+        out = rank_direct(buf, ld, V, cubes, amount)
+        check_rows(out, V, cubes, want, full, amount)
+        out = rank_direct(buf, ld, V, cubes, amount, want_scores=False, null_vals=True)
+        check_rows(out, V, cubes, want, full, amount, vals=False)
+
+
 def test_every_key_bit_decides_an_order():
     """Row 0 holds the 64 single-bit flips of 0.5: with the one-card cube [0] the score of card j
     is M[0][j] exactly, so the ranking depends on every bit of the key and every digit of every
