@@ -15,6 +15,7 @@ import numpy as np
 import torch
 
 from . import _lib as L
+from .launches import Staging, Workspace, mark, pipelined, row_spans, target_ranks_rows, upload
 from .recommender import RANK_STAGING_BYTES, check_card_ids, pack_cubes, pack_targets
 
 
@@ -26,6 +27,25 @@ def graph_rank_rows_per_launch(V, A, rows_per_launch, want_vals=True, want_score
     values (one f64 per cube card) are small beside them and not counted."""
     per_row = 4 + 4 * int(A) + (8 * int(A) if want_vals else 0) + (8 * int(V) if want_scores else 0)
     return max(1, min(int(rows_per_launch), int(budget_bytes) // per_row))
+
+
+def result_rows(Rc, A, row_ptr, idx, ints, addv, cutv, scores):
+    """The result dicts of one launch of Rc rows from its host arrays, the caller's own copies
+    (addv [Rc, A] and scores [Rc, V] may be None); the cube's cards are put into cut order here."""
+    nadd, adds = ints[:Rc].tolist(), ints[Rc:].reshape(Rc, A)
+    rows = []
+    for r in range(Rc):
+        k = nadd[r]
+        ids, vals = idx[row_ptr[r]:row_ptr[r + 1]], cutv[row_ptr[r]:row_ptr[r + 1]]
+        order = np.argsort(vals, kind='stable')     # about 360 values: the host's job
+        o = {'additions': adds[r, :k]}
+        if addv is not None:
+            o['add_vals'] = addv[r, :k]
+        o['cuts'], o['cut_vals'] = ids[order], vals[order]
+        if scores is not None:
+            o['scores'] = scores[r]
+        rows.append(o)
+    return rows
 
 
 class GraphRecommender:
@@ -51,9 +71,10 @@ class GraphRecommender:
         self.ld = int(a.stride(0)) if self.V > 1 else self.V
         self.stream = torch.cuda.Stream(device=self.dev)
         self.lock = threading.Lock()
-        self._ws = None
-        self._rank_ws = None    # rank_many's workspace (cc_graph_rank_ws_size) ...
-        self._rank_pins = {}    # ... and its two pinned staging sets
+        # one workspace serves every entry: cc_graph_rank_ws_size is never below cc_graph_rec_ws_size
+        # for the same rows (tests/test_graph_rank_host.py), and the lock admits one call at a time
+        self._ws = Workspace()
+        self._rank_pins = Staging()     # pinned staging; rank_many keeps two sets in it
         # requests run on the recommender's own stream: the matrix (an upload, or cc_adjacency on
         # another stream) must be complete before they can
         torch.cuda.synchronize(self.dev)
@@ -63,12 +84,6 @@ class GraphRecommender:
         """The graph of CSR cube lists, built on the device (adjacency.py: cc_adjacency's M)."""
         from .adjacency import adjacency_gpu
         return cls(adjacency_gpu(indptr, indices, V, ('M',), device=device)['M'])
-
-    def _workspace(self, Rc, max_n):
-        need = int(L.lib().cc_graph_rec_ws_size(self.V, Rc, max_n)) // 4 + 64
-        if self._ws is None or self._ws.numel() < need:
-            self._ws = torch.empty(need, device=self.dev, dtype=torch.int32)   # grown when needed, kept
-        return self._ws
 
     # ------------------------------------------------------------------ additions and cuts
     def recommend(self, cube_indices, amount, want_scores=False):
@@ -92,10 +107,9 @@ class GraphRecommender:
         launched (rank_many takes any amount and ranks every card; target_ranks serves
         evaluation)."""
         amount = int(amount)
-        rows_per_launch = max(1, int(rows_per_launch))
         inputs = [np.asarray(c, np.int64).reshape(-1) for c in cubes]
         R = len(inputs)
-        V, dev = self.V, getattr(self, 'dev', None)
+        V = self.V
         check_card_ids(inputs, V)
         cap = int(L.lib().cc_graph_rec_max_amount())
         if amount > cap:
@@ -103,51 +117,34 @@ class GraphRecommender:
         if R == 0:
             return []
         A = max(amount, 1)
+        dev, stage = self.dev, self._rank_pins
         out = []
 
-        def launch(r0, r1):
-            """Pack rows r0..r1, queue their launch and the copies of its results to pinned
+        def launch(r0, r1, turn):
+            """Pack rows r0..r1, queue their launch and the copies of its results to fresh pinned
             memory; no waiting."""
             row_ptr, idx, max_n, _, _ = pack_cubes(inputs[r0:r1], V)
             Rc, nnz = r1 - r0, len(idx)
-            ws = self._workspace(Rc, max_n)
-            rp_d = torch.from_numpy(row_ptr).to(dev, non_blocking=True)
-            ix_d = torch.from_numpy(idx if nnz else np.zeros(1, np.int32)).to(dev, non_blocking=True)
+            ws = self._ws.get(L.lib().cc_graph_rec_ws_size(V, Rc, max_n), dev)
+            rp_d, ix_d = upload(row_ptr, dev), upload(idx, dev)
             ints = torch.empty(Rc * (1 + A), device=dev, dtype=torch.int32)            # n_add, additions
             flts = torch.empty(Rc * A + max(nnz, 1), device=dev, dtype=torch.float64)  # add_vals, cut_vals
             scores = torch.empty(Rc, V, device=dev, dtype=torch.float64) if want_scores else None
             L.call('cc_graph_rec_f64', L.ptr(self.adj), self.ld, V, Rc, L.ptr(rp_d), L.ptr(ix_d), max_n,
                    amount, L.ptr(ws), L.ptr(ints), L.ptr(ints[Rc:]), L.ptr(flts), L.ptr(flts[Rc * A:]),
                    L.ptr(scores), L.stream_ptr(self.stream))
-            host = [torch.empty(t.shape, dtype=t.dtype, pin_memory=True).copy_(t, non_blocking=True)
-                    for t in ((ints, flts, scores) if want_scores else (ints, flts))]
-            done = torch.cuda.Event()
-            done.record(self.stream)
-            return r0, r1, row_ptr, idx, host, done
+            host = [stage.fresh(t) for t in ((ints, flts, scores) if want_scores else (ints, flts))]
+            return (row_ptr, idx, host), mark(self.stream)
 
-        def collect(r0, r1, row_ptr, idx, host, done):
-            done.synchronize()
+        def collect(r0, r1, payload):
+            row_ptr, idx, host = payload
             Rc = r1 - r0
-            ints, flts = host[0].numpy().copy(), host[1].numpy().copy()   # out of the pinned staging
-            nadd, adds, addv = ints[:Rc].tolist(), ints[Rc:].reshape(Rc, A), flts[:Rc * A].reshape(Rc, A)
-            cutv = flts[Rc * A:]
-            for r in range(Rc):
-                k = nadd[r]
-                ids, vals = idx[row_ptr[r]:row_ptr[r + 1]], cutv[row_ptr[r]:row_ptr[r + 1]]
-                order = np.argsort(vals, kind='stable')     # about 360 values: the host's job
-                o = {'additions': adds[r, :k], 'add_vals': addv[r, :k], 'cuts': ids[order], 'cut_vals': vals[order]}
-                if want_scores:
-                    o['scores'] = host[2][r].numpy().copy()
-                out.append(o)
+            ints, flts = host[0].numpy().copy(), host[1].numpy().copy()
+            out.extend(result_rows(Rc, A, row_ptr, idx, ints, flts[:Rc * A].reshape(Rc, A), flts[Rc * A:],
+                                   host[2].numpy().copy() if want_scores else None))
 
         with self.lock, torch.cuda.stream(self.stream):
-            pending = None      # a launch's results are unpacked while the next one runs
-            for r0 in range(0, R, rows_per_launch):
-                queued = launch(r0, min(R, r0 + rows_per_launch))
-                if pending is not None:
-                    collect(*pending)
-                pending = queued
-            collect(*pending)
+            pipelined(row_spans(R, rows_per_launch), launch, collect)
         return out
 
     # ------------------------------------------------------------------ every card, ranked
@@ -160,79 +157,47 @@ class GraphRecommender:
         by graph_rank_rows_per_launch, and their results pass through two pinned staging sets that
         the GraphRecommender keeps.  An id outside [0, V) raises ValueError naming the cube before
         anything is launched."""
-        rows_per_launch = max(1, int(rows_per_launch))
         inputs = [np.asarray(c, np.int64).reshape(-1) for c in cubes]
         R = len(inputs)
-        V, dev = self.V, getattr(self, 'dev', None)
+        V = self.V
         check_card_ids(inputs, V)
         if R == 0:
             return []
         amount = V if amount is None else int(amount)
         A = min(max(amount, 1), V)
         rows_per_launch = graph_rank_rows_per_launch(V, A, rows_per_launch, want_vals, want_scores)
-        if getattr(self, '_rank_pins', None) is None:
-            self._rank_pins = {}
-        pins = self._rank_pins
+        dev, stage = self.dev, self._rank_pins
         out = []
 
-        def staged(t, key):
-            """A view of the kept pinned buffer `key` (grown when needed) receiving `t`."""
-            if key not in pins or pins[key].numel() < t.numel():
-                pins[key] = torch.empty(t.numel(), dtype=t.dtype, pin_memory=True)
-            return pins[key][:t.numel()].view(t.shape).copy_(t, non_blocking=True)
-
         def launch(r0, r1, turn):
-            """Pack rows r0..r1, queue their launch and the copies of its results to pinned
-            memory (staging set `turn`); no waiting."""
+            """Pack rows r0..r1, queue their launch and the copies of its results to the kept
+            staging set of the turn's parity; no waiting."""
             row_ptr, idx, max_n, _, _ = pack_cubes(inputs[r0:r1], V)
             Rc, nnz = r1 - r0, len(idx)
-            need = int(L.lib().cc_graph_rank_ws_size(V, Rc, max_n)) // 4 + 64
-            if getattr(self, '_rank_ws', None) is None or self._rank_ws.numel() < need:
-                self._rank_ws = torch.empty(need, device=dev, dtype=torch.int32)   # grown when needed, kept
-            rp_d = torch.from_numpy(row_ptr).to(dev, non_blocking=True)
-            ix_d = torch.from_numpy(idx if nnz else np.zeros(1, np.int32)).to(dev, non_blocking=True)
+            ws = self._ws.get(L.lib().cc_graph_rank_ws_size(V, Rc, max_n), dev)
+            rp_d, ix_d = upload(row_ptr, dev), upload(idx, dev)
             ints = torch.empty(Rc * (1 + A), device=dev, dtype=torch.int32)            # n_add, additions
             vals = torch.empty(Rc * A, device=dev, dtype=torch.float64) if want_vals else None
             cutv = torch.empty(max(nnz, 1), device=dev, dtype=torch.float64)
             scores = torch.empty(Rc, V, device=dev, dtype=torch.float64) if want_scores else None
             L.call('cc_graph_rank_f64', L.ptr(self.adj), self.ld, V, Rc, L.ptr(rp_d), L.ptr(ix_d), max_n,
-                   amount, L.ptr(self._rank_ws), L.ptr(ints), L.ptr(ints[Rc:]), L.ptr(vals), L.ptr(cutv),
+                   amount, L.ptr(ws), L.ptr(ints), L.ptr(ints[Rc:]), L.ptr(vals), L.ptr(cutv),
                    L.ptr(scores), L.stream_ptr(self.stream))
-            host = {name: staged(t, (turn, name))
+            host = {name: stage.kept(t, (turn & 1, name))
                     for name, t in (('ints', ints), ('vals', vals), ('cutv', cutv), ('scores', scores))
                     if t is not None}
-            done = torch.cuda.Event()
-            done.record(self.stream)
-            return r0, r1, row_ptr, idx, host, done
+            return (row_ptr, idx, host), mark(self.stream)
 
-        def collect(r0, r1, row_ptr, idx, host, done):
-            done.synchronize()
+        def collect(r0, r1, payload):
+            row_ptr, idx, host = payload
             Rc = r1 - r0
             got = {name: t.numpy().copy() for name, t in host.items()}     # out of the pinned staging
-            ints, cutv = got['ints'], got['cutv']
-            nadd, adds = ints[:Rc].tolist(), ints[Rc:].reshape(Rc, A)
-            addv = got['vals'].reshape(Rc, A) if want_vals else None
-            for r in range(Rc):
-                k = nadd[r]
-                ids, vals = idx[row_ptr[r]:row_ptr[r + 1]], cutv[row_ptr[r]:row_ptr[r + 1]]
-                order = np.argsort(vals, kind='stable')     # about 360 values: the host's job
-                o = {'additions': adds[r, :k]}
-                if want_vals:
-                    o['add_vals'] = addv[r, :k]
-                o['cuts'], o['cut_vals'] = ids[order], vals[order]
-                if want_scores:
-                    o['scores'] = got['scores'][r]
-                out.append(o)
+            out.extend(result_rows(Rc, A, row_ptr, idx, got['ints'],
+                                   got['vals'].reshape(Rc, A) if want_vals else None, got['cutv'],
+                                   got.get('scores')))
 
         with self.lock, torch.cuda.stream(self.stream):
-            pending = None      # a launch's results are unpacked while the next one runs
-            for turn, r0 in enumerate(range(0, R, rows_per_launch)):
-                # a staging set is free again once the launch before last has been collected
-                queued = launch(r0, min(R, r0 + rows_per_launch), turn & 1)
-                if pending is not None:
-                    collect(*pending)
-                pending = queued
-            collect(*pending)
+            pipelined(row_spans(R, rows_per_launch), launch, collect)
         return out
 
     # ------------------------------------------------------------------ held-out evaluation
@@ -243,61 +208,24 @@ class GraphRecommender:
         evaluate.evaluate_holdout takes a GraphRecommender as its model: (ranks, vals, hits) with
         int32 ranks and float64 scores per cube in the caller's target order, hits None without
         cutoffs, else the device's uint64 counters [len(cutoffs) + 2]."""
-        rows_per_launch = max(1, int(rows_per_launch))
         cutoffs = [int(k) for k in cutoffs]
         if len(cutoffs) > 8:
             raise ValueError('at most 8 cutoffs')
         inputs = [np.asarray(c, np.int64).reshape(-1) for c in cubes]
         R = len(inputs)
-        V, dev = self.V, getattr(self, 'dev', None)
+        V = self.V
         check_card_ids(inputs, V)
         tgt_ptr, tgt = pack_targets(targets, inputs, V)
-        nk = len(cutoffs)
         if R == 0:
-            return [], [], (np.zeros(nk + 2, np.uint64) if nk else None)
-        ranks, vals = [], []
+            return [], [], (np.zeros(len(cutoffs) + 2, np.uint64) if cutoffs else None)
+        dev = self.dev
 
-        def launch(r0, r1):
-            row_ptr, idx, max_n, _, _ = pack_cubes(inputs[r0:r1], V)
-            Rc, nnz = r1 - r0, len(idx)
-            t0, t1 = int(tgt_ptr[r0]), int(tgt_ptr[r1])
-            tp = tgt_ptr[r0:r1 + 1] - tgt_ptr[r0]
-            nt = t1 - t0
-            ws = self._workspace(Rc, max_n)
-            rp_d = torch.from_numpy(row_ptr).to(dev, non_blocking=True)
-            ix_d = torch.from_numpy(idx if nnz else np.zeros(1, np.int32)).to(dev, non_blocking=True)
-            tp_d = torch.from_numpy(tp).to(dev, non_blocking=True)
-            tg_d = torch.from_numpy(tgt[t0:t1] if nt else np.zeros(1, np.int32)).to(dev, non_blocking=True)
-            rk = torch.empty(max(nt, 1), device=dev, dtype=torch.int32)
-            tv = torch.empty(max(nt, 1), device=dev, dtype=torch.float64)
-            cuts = torch.empty(max(nnz, 1), device=dev, dtype=torch.float64)   # the chain's; not returned
-            L.call('cc_graph_rec_target_ranks_f64', L.ptr(self.adj), self.ld, V, Rc, L.ptr(rp_d), L.ptr(ix_d),
-                   max_n, L.ptr(tp_d), L.ptr(tg_d), L.ptr(cut_d), nk, L.ptr(ws), L.ptr(rk), L.ptr(tv),
-                   L.ptr(hits_d), L.ptr(cuts), None, L.stream_ptr(self.stream))
-            host = [torch.empty(t.shape, dtype=t.dtype, pin_memory=True).copy_(t, non_blocking=True)
-                    for t in (rk, tv)]
-            done = torch.cuda.Event()
-            done.record(self.stream)
-            return r0, r1, host, done
-
-        def collect(r0, r1, host, done):
-            done.synchronize()
-            rk, tv = host[0].numpy(), host[1].numpy()
-            base = int(tgt_ptr[r0])
-            for r in range(r0, r1):
-                lo, hi = int(tgt_ptr[r]) - base, int(tgt_ptr[r + 1]) - base
-                ranks.append(rk[lo:hi].copy())
-                vals.append(tv[lo:hi].copy())
+        def call(s):
+            ws = self._ws.get(L.lib().cc_graph_rec_ws_size(V, s.Rc, s.max_n), dev)
+            L.call('cc_graph_rec_target_ranks_f64', L.ptr(self.adj), self.ld, V, s.Rc, L.ptr(s.rp), L.ptr(s.ix),
+                   s.max_n, L.ptr(s.tp), L.ptr(s.tg), L.ptr(s.cut), s.nk, L.ptr(ws), L.ptr(s.rk), L.ptr(s.tv),
+                   L.ptr(s.hits), L.ptr(s.cuts), None, L.stream_ptr(self.stream))
 
         with self.lock, torch.cuda.stream(self.stream):
-            cut_d = torch.tensor(cutoffs, device=dev, dtype=torch.int32) if nk else None
-            hits_d = torch.zeros(nk + 2, device=dev, dtype=torch.int64) if nk else None
-            pending = None      # a launch's results are unpacked while the next one runs
-            for r0 in range(0, R, rows_per_launch):
-                queued = launch(r0, min(R, r0 + rows_per_launch))
-                if pending is not None:
-                    collect(*pending)
-                pending = queued
-            collect(*pending)
-            hits = hits_d.cpu().numpy().view(np.uint64) if nk else None
-        return ranks, vals, hits
+            return target_ranks_rows(pack_cubes, inputs, V, tgt_ptr, tgt, cutoffs, rows_per_launch, dev,
+                                     self.stream, self._rank_pins, torch.float64, call)

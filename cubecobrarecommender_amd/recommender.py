@@ -12,6 +12,7 @@ import numpy as np
 import torch
 
 from . import _lib as L
+from .launches import Staging, Workspace, mark, pipelined, row_spans, target_ranks_rows, upload, ws_elems
 from .layout import Layout
 
 GRAPH_MAX_IDS = 4096   # cube ids per request the captured graph's H2D carries
@@ -186,6 +187,8 @@ def rank_rows_per_launch(V, A, rows_per_launch, budget_bytes=RANK_STAGING_BYTES,
 
 
 class Recommender:
+    _graph = None       # the captured request graph, once made (__del__ may meet a half-built object)
+
     def __init__(self, params_flat, V, d, device='cuda'):
         L.lib()
         self.V, self.d = int(V), int(d)
@@ -197,8 +200,7 @@ class Recommender:
         self.stream = torch.cuda.Stream(device=self.dev)
         self.lock = threading.Lock()
         self.probs_dev = torch.zeros(V, device=self.dev, dtype=torch.float32)
-        self.ws = torch.zeros(int(L.lib().cc_recommend_ws_size(V, d)) // 4 + 64,
-                              device=self.dev, dtype=torch.int32)
+        self.ws = torch.zeros(ws_elems(L.lib().cc_recommend_ws_size(V, d)), device=self.dev, dtype=torch.int32)
         # request I/O: req = {n, amount, ids[n]}, res = {n_add, additions, add_vals, cut_vals}
         self.cap = min(V, GRAPH_MAX_IDS)
         self.req_dev = torch.zeros(2 + V, device=self.dev, dtype=torch.int32)
@@ -207,17 +209,16 @@ class Recommender:
         self.pin_res = torch.zeros(1 + 2 * V + V, dtype=torch.int32).pin_memory()
         self._req_np = self.pin_req.numpy()
         self._res_np = self.pin_res.numpy()
-        self._graph = None
-        self._rank_pins = {}    # recommend_many's pinned staging on the full-ranking path
+        self._batch_ws = Workspace()    # the batched calls' workspace ...
+        self._rank_pins = Staging()     # ... and their pinned staging (kept on the full-ranking path)
         # the request graph runs on the library's own non-blocking stream: every allocation and
         # fill above (issued on torch's stream) must be complete before it can run
         torch.cuda.synchronize(self.dev)
 
     def __del__(self):
-        g = getattr(self, '_graph', None)
-        if g is not None:
+        if self._graph is not None:
             try:
-                L.lib().cc_recommend_graph_destroy(g)
+                L.lib().cc_recommend_graph_destroy(self._graph)
             except Exception:
                 pass
 
@@ -349,7 +350,6 @@ class Recommender:
         probs do not depend on the pool, nor does the choice of path.  A pool built for another V
         or a sequence of another length raises ValueError before anything is launched."""
         amount = int(amount)
-        rows_per_launch = max(1, int(rows_per_launch))
         inputs = [np.asarray(c, np.int64).reshape(-1) for c in cubes]
         R = len(inputs)
         pools, pool_of_row = resolve_pools(pool, R, self.V)
@@ -367,46 +367,33 @@ class Recommender:
             rows_per_launch = rank_rows_per_launch(V, A, rows_per_launch, want_probs=want_probs)
         else:
             A = max(amount, 1)
+        stage = self._rank_pins
         out = []
-
-        def staged(t, key):
-            """A pinned host tensor receiving `t`: fresh on the select path; on the ranking path
-            a view of the kept buffer `key`, which grows when needed."""
-            if not rank:
-                return torch.empty(t.shape, dtype=t.dtype, pin_memory=True).copy_(t, non_blocking=True)
-            pins = self._rank_pins
-            if key not in pins or pins[key].numel() < t.numel():
-                pins[key] = torch.empty(t.numel(), dtype=t.dtype, pin_memory=True)
-            return pins[key][:t.numel()].view(t.shape).copy_(t, non_blocking=True)
 
         def launch(r0, r1, turn):
             """Pack rows r0..r1, queue their launch and the copies of its results to pinned
-            memory (staging set `turn`); no waiting."""
+            memory (fresh on the select path, the kept staging set of the turn's parity on the
+            ranking path); no waiting."""
             row_ptr, idx, max_n, _, slot = pack_cubes(inputs[r0:r1], V)
             Rc, nnz = r1 - r0, len(idx)
-            need = int(ws_size(V, d, Rc, max_n)) // 4 + 64
-            if getattr(self, '_batch_ws', None) is None or self._batch_ws.numel() < need:
-                self._batch_ws = torch.empty(need, device=dev, dtype=torch.int32)   # grown when needed, kept
-            rp_d = torch.from_numpy(row_ptr).to(dev, non_blocking=True)
-            ix_d = torch.from_numpy(idx if nnz else np.zeros(1, np.int32)).to(dev, non_blocking=True)
+            ws = self._batch_ws.get(ws_size(V, d, Rc, max_n), dev)
+            rp_d, ix_d = upload(row_ptr, dev), upload(idx, dev)
             ints = torch.empty(Rc * (1 + A), device=dev, dtype=torch.int32)      # n_add, additions
             flts = torch.empty(Rc * A + max(nnz, 1), device=dev, dtype=torch.float32)  # add_vals, cuts
             probs = torch.empty(Rc, V, device=dev, dtype=torch.float32) if want_probs else None
             pool_args = ()
             if pools is not None:
-                por_d = torch.from_numpy(pool_of_row[r0:r1]).to(dev, non_blocking=True)
+                por_d = upload(pool_of_row[r0:r1], dev)
                 pool_args = (L.ptr(table), len(pools), L.ptr(por_d))
             L.call(entry, L.ptr(self.params), V, d, Rc, L.ptr(rp_d), L.ptr(ix_d), max_n,
-                   amount, L.ptr(self._batch_ws), L.ptr(ints), L.ptr(ints[Rc:]), L.ptr(flts),
+                   amount, L.ptr(ws), L.ptr(ints), L.ptr(ints[Rc:]), L.ptr(flts),
                    L.ptr(flts[Rc * A:]), L.ptr(probs), *pool_args, L.stream_ptr(self.stream))
-            host = [staged(t, (turn, i))
+            host = [stage.kept(t, (turn & 1, i)) if rank else stage.fresh(t)
                     for i, t in enumerate((ints, flts, probs) if want_probs else (ints, flts))]
-            done = torch.cuda.Event()
-            done.record(self.stream)
-            return r0, r1, nnz, slot, host, done
+            return (nnz, slot, host), mark(self.stream)
 
-        def collect(r0, r1, nnz, slot, host, done):
-            done.synchronize()
+        def collect(r0, r1, payload):
+            nnz, slot, host = payload
             Rc = r1 - r0
             ints, flts = host[0].numpy().copy(), host[1].numpy().copy()   # out of the pinned staging
             nadd, adds, addv = ints[:Rc].tolist(), ints[Rc:].reshape(Rc, A), flts[:Rc * A].reshape(Rc, A)
@@ -420,14 +407,7 @@ class Recommender:
 
         with self.lock, torch.cuda.stream(self.stream):
             table = self._pool_table(pools) if pools is not None else None
-            pending = None      # a launch's results are unpacked while the next one runs
-            for turn, r0 in enumerate(range(0, R, rows_per_launch)):
-                # a staging set is free again once the launch before last has been collected
-                queued = launch(r0, min(R, r0 + rows_per_launch), turn & 1)
-                if pending is not None:
-                    collect(*pending)
-                pending = queued
-            collect(*pending)
+            pipelined(row_spans(R, rows_per_launch), launch, collect)
         return out
 
     # ------------------------------------------------------------------ held-out evaluation
@@ -449,7 +429,6 @@ class Recommender:
         (cc_recommend_batch_target_ranks_pool_fp32); a target outside its row's pool raises
         ValueError naming the cube and the card, as do a pool built for another V and a sequence
         of another length, all before anything is launched."""
-        rows_per_launch = max(1, int(rows_per_launch))
         cutoffs = [int(k) for k in cutoffs]
         if len(cutoffs) > 8:
             raise ValueError('at most 8 cutoffs')
@@ -461,68 +440,26 @@ class Recommender:
         tgt_ptr, tgt = pack_targets(targets, inputs, V)
         if pools is not None:
             check_targets_in_pools(targets, pools, pool_of_row)
-        nk = len(cutoffs)
         if R == 0:
-            return [], [], (np.zeros(nk + 2, np.uint64) if nk else None)
+            return [], [], (np.zeros(len(cutoffs) + 2, np.uint64) if cutoffs else None)
         dev = self.dev
         stem = 'cc_recommend_batch_target_ranks' + ('_pool' if pools is not None else '')
         entry, ws_size = stem + '_fp32', getattr(L.lib(), stem + '_ws_size')
-        ranks, vals = [], []
 
-        def launch(r0, r1):
-            """Pack rows r0..r1, queue their launch and the copies of its results to pinned
-            memory; no waiting."""
-            row_ptr, idx, max_n, _, _ = pack_cubes(inputs[r0:r1], V)
-            Rc, nnz = r1 - r0, len(idx)
-            t0, t1 = int(tgt_ptr[r0]), int(tgt_ptr[r1])
-            tp = tgt_ptr[r0:r1 + 1] - tgt_ptr[r0]
-            nt = t1 - t0
-            need = int(ws_size(V, d, Rc, max_n)) // 4 + 64
-            if getattr(self, '_batch_ws', None) is None or self._batch_ws.numel() < need:
-                self._batch_ws = torch.empty(need, device=dev, dtype=torch.int32)   # grown when needed, kept
-            rp_d = torch.from_numpy(row_ptr).to(dev, non_blocking=True)
-            ix_d = torch.from_numpy(idx if nnz else np.zeros(1, np.int32)).to(dev, non_blocking=True)
-            tp_d = torch.from_numpy(tp).to(dev, non_blocking=True)
-            tg_d = torch.from_numpy(tgt[t0:t1] if nt else np.zeros(1, np.int32)).to(dev, non_blocking=True)
-            rk = torch.empty(max(nt, 1), device=dev, dtype=torch.int32)
-            tv = torch.empty(max(nt, 1), device=dev, dtype=torch.float32)
-            cuts = torch.empty(max(nnz, 1), device=dev, dtype=torch.float32)   # the chain's; not returned
+        def call(s):
             pool_args = ()
             if pools is not None:
-                por_d = torch.from_numpy(pool_of_row[r0:r1]).to(dev, non_blocking=True)
+                por_d = upload(pool_of_row[s.r0:s.r1], dev)
                 pool_args = (L.ptr(table), len(pools), L.ptr(por_d))
-            L.call(entry, L.ptr(self.params), V, d, Rc, L.ptr(rp_d),
-                   L.ptr(ix_d), max_n, L.ptr(tp_d), L.ptr(tg_d), L.ptr(cut_d), nk, L.ptr(self._batch_ws),
-                   L.ptr(rk), L.ptr(tv), L.ptr(hits_d), L.ptr(cuts), None, *pool_args,
-                   L.stream_ptr(self.stream))
-            host = [torch.empty(t.shape, dtype=t.dtype, pin_memory=True).copy_(t, non_blocking=True)
-                    for t in (rk, tv)]
-            done = torch.cuda.Event()
-            done.record(self.stream)
-            return r0, r1, host, done
-
-        def collect(r0, r1, host, done):
-            done.synchronize()
-            rk, tv = host[0].numpy(), host[1].numpy()
-            base = int(tgt_ptr[r0])
-            for r in range(r0, r1):
-                lo, hi = int(tgt_ptr[r]) - base, int(tgt_ptr[r + 1]) - base
-                ranks.append(rk[lo:hi].copy())
-                vals.append(tv[lo:hi].copy())
+            ws = self._batch_ws.get(ws_size(V, d, s.Rc, s.max_n), dev)
+            L.call(entry, L.ptr(self.params), V, d, s.Rc, L.ptr(s.rp), L.ptr(s.ix), s.max_n, L.ptr(s.tp),
+                   L.ptr(s.tg), L.ptr(s.cut), s.nk, L.ptr(ws), L.ptr(s.rk), L.ptr(s.tv), L.ptr(s.hits),
+                   L.ptr(s.cuts), None, *pool_args, L.stream_ptr(self.stream))
 
         with self.lock, torch.cuda.stream(self.stream):
             table = self._pool_table(pools) if pools is not None else None
-            cut_d = torch.tensor(cutoffs, device=dev, dtype=torch.int32) if nk else None
-            hits_d = torch.zeros(nk + 2, device=dev, dtype=torch.int64) if nk else None
-            pending = None      # a launch's results are unpacked while the next one runs
-            for r0 in range(0, R, rows_per_launch):
-                queued = launch(r0, min(R, r0 + rows_per_launch))
-                if pending is not None:
-                    collect(*pending)
-                pending = queued
-            collect(*pending)
-            hits = hits_d.cpu().numpy().view(np.uint64) if nk else None
-        return ranks, vals, hits
+            return target_ranks_rows(pack_cubes, inputs, V, tgt_ptr, tgt, cutoffs, rows_per_launch, dev,
+                                     self.stream, self._rank_pins, torch.float32, call)
 
     # ------------------------------------------------------------------ validation loss
     def reconstruction_loss(self, cubes, targets=None, rows_per_launch=512):
@@ -537,10 +474,9 @@ class Recommender:
         categorical accuracy compares it with the first target).  targets=None means the cubes
         themselves.  Duplicates collapse in both lists; an id outside [0, V) in either raises
         ValueError before anything is launched."""
-        rows_per_launch = max(1, int(rows_per_launch))
         inputs = [np.asarray(c, np.int64).reshape(-1) for c in cubes]
         R = len(inputs)
-        V, d, dev = self.V, self.d, self.dev
+        V, d = self.V, self.d
         check_card_ids(inputs, V)
         if targets is None:
             tgts = inputs
@@ -552,48 +488,30 @@ class Recommender:
         row_loss, row_pred = np.zeros(R, np.float64), np.zeros(R, np.int32)
         if R == 0:
             return row_loss, row_pred
-        ws_size = L.lib().cc_recommend_batch_loss_ws_size
+        dev, stage = self.dev, self._rank_pins
 
-        def launch(r0, r1):
+        def launch(r0, r1, turn):
             """Pack rows r0..r1, queue their launch and the copies of its results to pinned
             memory; no waiting."""
             row_ptr, idx, max_n, _, _ = pack_cubes(inputs[r0:r1], V)
-            tgt_ptr, tgt = (row_ptr, idx) if targets is None else pack_cubes(tgts[r0:r1], V)[:2]
             Rc = r1 - r0
-            need = int(ws_size(V, d, Rc, max_n)) // 4 + 64
-            if getattr(self, '_batch_ws', None) is None or self._batch_ws.numel() < need:
-                self._batch_ws = torch.empty(need, device=dev, dtype=torch.int32)   # grown when needed, kept
-            rp_d = torch.from_numpy(row_ptr).to(dev, non_blocking=True)
-            ix_d = torch.from_numpy(idx if len(idx) else np.zeros(1, np.int32)).to(dev, non_blocking=True)
-            if targets is None:
-                tp_d, tg_d = rp_d, ix_d
-            else:
-                tp_d = torch.from_numpy(tgt_ptr).to(dev, non_blocking=True)
-                tg_d = torch.from_numpy(tgt if len(tgt) else np.zeros(1, np.int32)).to(dev, non_blocking=True)
+            ws = self._batch_ws.get(L.lib().cc_recommend_batch_loss_ws_size(V, d, Rc, max_n), dev)
+            tp_d, tg_d = rp_d, ix_d = upload(row_ptr, dev), upload(idx, dev)
+            if targets is not None:
+                tgt_ptr, tgt = pack_cubes(tgts[r0:r1], V)[:2]
+                tp_d, tg_d = upload(tgt_ptr, dev), upload(tgt, dev)
             loss = torch.empty(Rc, device=dev, dtype=torch.float64)
             pred = torch.empty(Rc, device=dev, dtype=torch.int32)
             L.call('cc_recommend_batch_loss_fp32', L.ptr(self.params), V, d, Rc, L.ptr(rp_d), L.ptr(ix_d), max_n,
-                   L.ptr(tp_d), L.ptr(tg_d), L.ptr(self._batch_ws), L.ptr(loss), L.ptr(pred),
-                   L.stream_ptr(self.stream))
-            host = [torch.empty(t.shape, dtype=t.dtype, pin_memory=True).copy_(t, non_blocking=True)
-                    for t in (loss, pred)]
-            done = torch.cuda.Event()
-            done.record(self.stream)
-            return r0, r1, host, done
+                   L.ptr(tp_d), L.ptr(tg_d), L.ptr(ws), L.ptr(loss), L.ptr(pred), L.stream_ptr(self.stream))
+            return (stage.fresh(loss), stage.fresh(pred)), mark(self.stream)
 
-        def collect(r0, r1, host, done):
-            done.synchronize()
+        def collect(r0, r1, host):
             row_loss[r0:r1] = host[0].numpy()
             row_pred[r0:r1] = host[1].numpy()
 
         with self.lock, torch.cuda.stream(self.stream):
-            pending = None      # a launch's results are unpacked while the next one runs
-            for r0 in range(0, R, rows_per_launch):
-                queued = launch(r0, min(R, r0 + rows_per_launch))
-                if pending is not None:
-                    collect(*pending)
-                pending = queued
-            collect(*pending)
+            pipelined(row_spans(R, rows_per_launch), launch, collect)
         return row_loss, row_pred
 
     def _full_order(self, probs, uniq, amount):
@@ -607,7 +525,7 @@ class Recommender:
         cutv = torch.zeros(max(n, 1), device=dev)
         nadd = torch.zeros(1, device=dev, dtype=torch.int32)
         order = torch.zeros(V, device=dev, dtype=torch.int32)
-        ws = torch.zeros(int(L.lib().cc_topn_workspace_size(V)) // 4 + 64, device=dev, dtype=torch.int32)
+        ws = torch.zeros(ws_elems(L.lib().cc_topn_workspace_size(V)), device=dev, dtype=torch.int32)
         L.call('cc_topn', L.ptr(probs), V, L.ptr(ci), n, amount, L.ptr(adds), L.ptr(nadd), L.ptr(addv),
                L.ptr(cutv), L.ptr(order), L.ptr(ws), L.stream_ptr())
         torch.cuda.synchronize()

@@ -10,6 +10,7 @@ import numpy as np
 import torch
 
 from . import _lib as L
+from .launches import Staging, Workspace, mark, pipelined, row_spans, upload
 
 
 def card_embeddings(model):
@@ -60,15 +61,8 @@ def similar_cards(model, name, N, int_to_card, card_to_int):
 
 # ---------------------------------------------------------------------- many query cards per call
 _ws_lock = threading.Lock()
-_ws = {}          # device -> the batched entry's workspace: grown when needed, kept
-
-
-def _workspace(dev, V, K, Q, N):
-    need = int(L.lib().cc_similar_batch_ws_size(V, K, Q, N)) // 4 + 64
-    ws = _ws.get(dev)
-    if ws is None or ws.numel() < need:
-        ws = _ws[dev] = torch.empty(need, device=dev, dtype=torch.int32)
-    return ws
+_ws = {}          # device -> the batched entry's Workspace
+_stage = Staging()
 
 
 def _similar_rows(emb, queries, n, rows_per_launch, idx_dtype):
@@ -79,34 +73,25 @@ def _similar_rows(emb, queries, n, rows_per_launch, idx_dtype):
     Q, dev = len(queries), emb.device
     out_i, out_d = np.empty((Q, n), idx_dtype), np.empty((Q, n), np.float32)
 
-    def launch(r0, r1):
+    def launch(r0, r1, turn):
         Rc = r1 - r0
-        ws = _workspace(dev, V, K, Rc, n)
-        q_d = torch.from_numpy(queries[r0:r1]).to(dev, non_blocking=True)
+        ws = kept.get(L.lib().cc_similar_batch_ws_size(V, K, Rc, n), dev)
+        q_d = upload(queries[r0:r1], dev)
         idx = torch.empty(Rc, n, device=dev, dtype=torch.int32)
         dist = torch.empty(Rc, n, device=dev, dtype=torch.float32)
         L.call('cc_similar_cards_batch', L.ptr(emb), V, K, Rc, L.ptr(q_d), n, L.ptr(ws), L.ptr(idx),
                L.ptr(dist), None, L.stream_ptr())
-        host = [torch.empty(t.shape, dtype=t.dtype, pin_memory=True).copy_(t, non_blocking=True)
-                for t in (idx, dist)]
-        done = torch.cuda.Event()
-        done.record()
-        return r0, r1, host, done
+        return (_stage.fresh(idx), _stage.fresh(dist)), mark()
 
-    def collect(r0, r1, host, done):
-        done.synchronize()
+    def collect(r0, r1, host):
         out_i[r0:r1] = host[0].numpy()
         out_d[r0:r1] = host[1].numpy()
 
     with _ws_lock:        # one workspace per device: one caller at a time
-        pending = None
-        for r0 in range(0, Q, rows_per_launch):
-            queued = launch(r0, min(Q, r0 + rows_per_launch))
-            if pending is not None:
-                collect(*pending)
-            pending = queued
-        collect(*pending)
+        kept = _ws.setdefault(dev, Workspace())
+        last = pipelined(row_spans(Q, rows_per_launch), launch, collect)
         torch.cuda.current_stream().synchronize()   # the workspace is free for the next caller's stream
+        del last    # only now: freeing pinned memory records an event on the stream (16 us inside the wait)
     return out_i, out_d
 
 
@@ -123,7 +108,7 @@ def similar_many(emb, idxs, N, rows_per_launch=512):
     n = max(0, min(int(N), V))
     if n == 0 or len(q) == 0:
         return np.zeros((len(q), n), np.int64), np.zeros((len(q), n), np.float32)
-    return _similar_rows(emb.contiguous(), q.astype(np.int32), n, max(1, int(rows_per_launch)), np.int64)
+    return _similar_rows(emb.contiguous(), q.astype(np.int32), n, rows_per_launch, np.int64)
 
 
 def similar_cards_many(model, names, N, int_to_card, card_to_int):
@@ -143,5 +128,4 @@ def similarity_table(model_or_emb, N, rows_per_launch=512):
     n = max(0, min(int(N), V))
     if n == 0:
         return np.zeros((V, 0), np.int32), np.zeros((V, 0), np.float32)
-    return _similar_rows(emb.contiguous(), np.arange(V, dtype=np.int32), n, max(1, int(rows_per_launch)),
-                         np.int32)
+    return _similar_rows(emb.contiguous(), np.arange(V, dtype=np.int32), n, rows_per_launch, np.int32)

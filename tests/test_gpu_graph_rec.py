@@ -209,7 +209,7 @@ def test_batching(pad):
         assert np.array_equal(o['cuts'], ec) and np.array_equal(bits(o['cut_vals']), bits(ecv)), r
         assert np.array_equal(bits(o['scores']), bits(s)), r
     for split in (512, 64, 7):
-        rec._ws.fill_(-1)
+        rec._ws.buf.fill_(-1)
         torch.cuda.synchronize()                                           # the fill ran on another stream
         again = rec.recommend_many(cubes, 100, rows_per_launch=split)          # without the scores
         assert len(again) == 130 and all(same(a, b) for a, b in zip(again, base)) and 'scores' not in again[0]
