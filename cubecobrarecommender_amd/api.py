@@ -89,6 +89,15 @@ def recommend_many(model, cubes_indices, amount, int_to_card, pool=None):
     return result
 
 
+def similar_cubes(index, cube_indices, k, cube_names=None):
+    """"Cubes like this one" for one fresh cube given as card ids, against a cubesim.CubeIndex
+    (model.cube_index(cubes)): [(rank, cube, dist)] for ranks 1..min(k, len(index)), nearest first;
+    cube is the index's cube id, or cube_names[id] with cube_names (a sequence or a dict)."""
+    idx, dists = index.neighbours_of([list(cube_indices)], k)
+    return [(i + 1, int(j) if cube_names is None else cube_names[int(j)], float(dv))
+            for i, (j, dv) in enumerate(zip(idx[0], dists[0]))]
+
+
 def _graph_of(adj_mtx):
     """adj_mtx as a GraphRecommender: one passed in is used as it is (its graph stays resident);
     a matrix is uploaded for this call."""

@@ -1,0 +1,520 @@
+// cc_cube_index_put / cc_cube_neighbours — a resident index of cube embeddings and the exact k
+// nearest cubes of Q queries over it.  The arithmetic is card similarity's (similarity.hip,
+// simbatch.hip, oracle/similarity_ref.py): fp32, multiply and add separately rounded,
+// ss = sum e[i]^2 in index order, inv = 1/sqrt(max(ss, 1e-12)), n[i] = e[i] * inv,
+// dist = -sum n_q[i] * n_j[i] in index order from +0; ranking by ascending composite
+// (orderable(dist) << 32 | cube), which is unique: numpy argsort(kind='stable').
+//
+// The index is n [cap][Kp] (row-major, for member queries) and nT [Kp][caps] (k-major, for the
+// corpus side of the distance tile), Kp = K rounded up to the tile's k stage, caps = cap rounded
+// up to 64.  It is written by puts alone and normalised once:
+//   put_rows_kernel   : simbatch.hip's normalise_kernel at a row offset.  One thread per row, so a
+//                       row's bits do not depend on where a put starts or ends; the k pad of the
+//                       rows it writes is written as zeros.
+// A search runs, once per call,
+//   query_rows_kernel : one 64-thread workgroup per query.  A member's row is copied from n, a
+//                       fresh embedding is normalised by put's arithmetic (staged through LDS, the
+//                       sum by one thread in index order), into qn [Q][Kp]; qok [Q] says whether the
+//                       row is a query at all (an id outside [0, N) never is).
+// then per chunk of the corpus (cubes [c0, c0 + cl)), so that the keys are [Q][chunk], never [Q][N],
+//   dist_chunk_kernel : simbatch.hip's distance tile, 16*RM queries x 64 cubes per workgroup, the
+//                       query rows from qn, the cubes from nT at c0.  Writes orderable(-dot).
+//   select_chunk_kernel: one workgroup per query.  The chunk's min(k, population) smallest
+//                       composites, the row's skip left out, by the radix select and bitonic sort
+//                       of select_rows_kernel, stored with global cube ids as candidates
+//                       [Q][chunks][k]; unused slots hold a sentinel above every composite.
+// and at the end
+//   merge_rows_kernel : one workgroup per query.  The same select over the row's k * chunks
+//                       candidates; writes the first min(k, candidates) ids and distances and the
+//                       -1 / 0.f tail.  A corpus of one chunk needs no merge: its select writes
+//                       the rows itself.
+// Every cube is a candidate of exactly one chunk and a chunk keeps its k smallest, so the k
+// smallest of the row are among the candidates whatever the chunk size; the composite order is
+// total, so no output bit depends on the chunk, the batch or the launch.
+#include <algorithm>
+
+#include "common.hpp"
+#include "detmath.hpp"
+#include "rowsort.hpp"
+
+namespace {
+
+constexpr int KS = 32;        // k per LDS stage of the distance tile
+constexpr int TC = 64;        // cubes per distance tile
+constexpr int DNT = 256;      // distance-tile workgroup: 16 cube groups x 16 query groups
+constexpr int NR = 128;       // put: rows per workgroup, one thread each
+constexpr int QNT = 64;       // query rows: one thread each
+constexpr int SNT = 1024;     // select workgroup
+constexpr int MAX_K = 1024;   // neighbours per query
+constexpr int MAX_SEL = 2048; // survivors sorted in LDS
+constexpr int MAX_Q = 1 << 22;
+constexpr int DEFAULT_CHUNK = 1 << 16;
+constexpr uint64_t NONE = ~0ull;  // no candidate: above every composite of a finite distance
+
+using detm::addf;
+using detm::mulf;
+using rowsort::orderable;
+
+// orderable's inverse on distances: the only zero a distance takes is -0.0f (simbatch.hip)
+__device__ __forceinline__ float dist_of_key(uint32_t key) {
+  if (key == 0x80000000u) return __uint_as_float(0x80000000u);
+  return __uint_as_float((key & 0x80000000u) ? (key & 0x7FFFFFFFu) : ~key);
+}
+
+__device__ __forceinline__ float inv_norm(float ss) { return 1.f / sqrtf(fmaxf(ss, 1e-12f)); }
+
+// A 128 x 32 tile of z into LDS, zeros outside [0, rows) x [0, K) (simbatch.hip's stage_tile).
+__device__ __forceinline__ void stage_tile(float (*tile)[KS + 1], const float *__restrict__ z, int rows,
+                                           int K, int r0, int k0) {
+  static_assert(NR % KS == 0, "a thread keeps its column: step u holds rows u * NR / KS + tid / KS");
+  const int c = threadIdx.x % KS, rq = threadIdx.x / KS;
+  const bool col_ok = k0 + c < K;
+  float x[KS];
+#pragma unroll
+  for (int u = 0; u < KS; ++u) {
+    const int r = u * (NR / KS) + rq;
+    const bool ok = col_ok && r0 + r < rows;
+    const float v = z[ok ? (int64_t)(r0 + r) * K + k0 + c : 0];
+    x[u] = ok ? v : 0.f;
+  }
+#pragma unroll
+  for (int u = 0; u < KS; ++u) tile[u * (NR / KS) + rq][c] = x[u];
+}
+
+// rows of z -> index rows [n0, n0 + rows): n [.][Kp] and nT [Kp][caps]
+__global__ __launch_bounds__(NR) void put_rows_kernel(const float *__restrict__ z, int rows, int K, int Kp,
+                                                      int caps, int n0, float *__restrict__ n,
+                                                      float *__restrict__ nT) {
+  __shared__ float tile[NR][KS + 1];
+  const int tid = threadIdx.x;
+  const int r0 = blockIdx.x * NR, row = r0 + tid;
+  float ss = 0.f;
+  for (int k0 = 0; k0 < Kp; k0 += KS) {
+    __syncthreads();  // the previous stage's readers are done
+    stage_tile(tile, z, rows, K, r0, k0);
+    __syncthreads();
+    const int kc = min(KS, K - k0);
+    for (int c = 0; c < kc; ++c) {
+      const float x = tile[tid][c];
+      ss = addf(ss, mulf(x, x));
+    }
+  }
+  const float inv = inv_norm(ss);
+  for (int k0 = 0; k0 < Kp; k0 += KS) {
+    __syncthreads();
+    stage_tile(tile, z, rows, K, r0, k0);
+    __syncthreads();
+#pragma unroll 8
+    for (int c = 0; c < KS; ++c) {
+      const float v = mulf(tile[tid][c], inv);
+      tile[tid][c] = v;
+      if (row < rows) nT[(int64_t)(k0 + c) * caps + n0 + row] = v;
+    }
+    __syncthreads();
+    for (int t = tid; t < NR * KS; t += NR) {
+      const int r = t / KS, c = t % KS;
+      if (r0 + r < rows) n[(int64_t)(n0 + r0 + r) * Kp + k0 + c] = tile[r][c];
+    }
+  }
+}
+
+// Query r (one workgroup each): the index row qid[r] (0 <= qid[r] < N), else the raw embedding
+// zq[r] (a negative or absent id, zq given), else none.
+__global__ __launch_bounds__(QNT) void query_rows_kernel(const float *__restrict__ n, int N, int K, int Kp,
+                                                         const int32_t *__restrict__ qid,
+                                                         const float *__restrict__ zq,
+                                                         float *__restrict__ qn, int32_t *__restrict__ qok) {
+  __shared__ float stage[QNT];
+  __shared__ float s_inv;
+  const int r = blockIdx.x, tid = threadIdx.x;
+  const int id = qid ? qid[r] : -1;  // (block-uniform, as is every branch below)
+  float *out = qn + (int64_t)r * Kp;
+  if ((uint32_t)id < (uint32_t)N) {
+    const float *src = n + (int64_t)id * Kp;
+    for (int i = tid; i < Kp; i += QNT) out[i] = src[i];
+  } else if (id < 0 && zq) {
+    const float *e = zq + (int64_t)r * K;
+    float ss = 0.f;  // thread 0's: the pinned order is sequential
+    for (int k0 = 0; k0 < K; k0 += QNT) {
+      __syncthreads();  // the previous stage is summed
+      if (k0 + tid < K) stage[tid] = e[k0 + tid];
+      __syncthreads();
+      if (tid == 0)
+        for (int c = 0; c < min(QNT, K - k0); ++c) ss = addf(ss, mulf(stage[c], stage[c]));
+    }
+    if (tid == 0) s_inv = inv_norm(ss);
+    __syncthreads();
+    const float inv = s_inv;
+    for (int i = tid; i < Kp; i += QNT) out[i] = i < K ? mulf(e[i], inv) : 0.f;
+  }
+  if (tid == 0) qok[r] = ((uint32_t)id < (uint32_t)N || (id < 0 && zq)) ? 1 : 0;
+}
+
+// keys [Q][pitch] of the chunk's cubes [c0, c0 + cl): key (r, j) = orderable(-dot(qn[r], n[c0 + j]))
+// (4 waves per SIMD, as simbatch.hip's tile has at RM = 8: at most 128 VGPRs)
+template <int RM>
+__global__ __launch_bounds__(DNT, 4) void dist_chunk_kernel(const float *__restrict__ qn,
+                                                            const int32_t *__restrict__ qok,
+                                                            const float *__restrict__ nT, int caps, int c0,
+                                                            int cl, int Kp, int Q, int pitch,
+                                                            uint32_t *__restrict__ keys) {
+  constexpr int TR = 16 * RM;
+  constexpr int F4 = KS / 4, RS = DNT / F4;  // float4 per query row, query rows per step
+  __shared__ __attribute__((aligned(16))) float wsm[KS][TC];
+  __shared__ __attribute__((aligned(16))) float hsm[TR][KS];
+  const int tid = threadIdx.x;
+  const int tx = tid & 15, ty = tid >> 4;
+  const int nb = blockIdx.x * TC;  // first cube of the tile, inside the chunk
+  const int rb = blockIdx.y * TR;  // first query of the tile
+  float acc[RM][4];
+#pragma unroll
+  for (int j = 0; j < RM; ++j)
+#pragma unroll
+    for (int e = 0; e < 4; ++e) acc[j][e] = 0.f;
+  // the rows this thread stages are RS rows of qn apart: one pointer, and a bit per row that is
+  // inside Q and a query
+  const float *qbase = qn + (int64_t)(rb + tid / F4) * Kp + 4 * (tid % F4);
+  uint32_t qmask = 0u;
+#pragma unroll
+  for (int i = 0; i < TR / RS; ++i) {
+    const int gr = rb + tid / F4 + RS * i;
+    if (gr < Q && qok[gr] != 0) qmask |= 1u << i;
+  }
+
+  for (int k0 = 0; k0 < Kp; k0 += KS) {
+    __syncthreads();  // the previous stage's readers are done
+    {
+      const int c = tid & 63, gn = nb + c;
+      const float *Wp = nT + ((int64_t)k0 + (tid >> 6)) * caps + c0 + gn;
+      float w[KS / 4];
+#pragma unroll
+      for (int i = 0; i < KS / 4; ++i) w[i] = gn < cl ? Wp[(int64_t)(4 * i) * caps] : 0.f;
+      float4 h[TR / RS];
+#pragma unroll
+      for (int i = 0; i < TR / RS; ++i)
+        h[i] = (qmask >> i) & 1u ? *reinterpret_cast<const float4 *>(qbase + (int64_t)(RS * i) * Kp + k0)
+                                 : make_float4(0.f, 0.f, 0.f, 0.f);
+#pragma unroll
+      for (int i = 0; i < KS / 4; ++i) wsm[4 * i + (tid >> 6)][c] = w[i];
+#pragma unroll
+      for (int i = 0; i < TR / RS; ++i)
+        *reinterpret_cast<float4 *>(&hsm[tid / F4 + RS * i][4 * (tid % F4)]) = h[i];
+    }
+    __syncthreads();
+#pragma unroll 2
+    for (int k4 = 0; k4 < KS / 4; ++k4) {
+      float4 w[4];
+#pragma unroll
+      for (int kk = 0; kk < 4; ++kk) w[kk] = *reinterpret_cast<const float4 *>(&wsm[4 * k4 + kk][4 * tx]);
+#pragma unroll
+      for (int j = 0; j < RM; ++j) {
+        const float4 h = *reinterpret_cast<const float4 *>(&hsm[ty * RM + j][4 * k4]);
+        const float hk[4] = {h.x, h.y, h.z, h.w};
+#pragma unroll
+        for (int kk = 0; kk < 4; ++kk) {
+          acc[j][0] = addf(acc[j][0], mulf(hk[kk], w[kk].x));
+          acc[j][1] = addf(acc[j][1], mulf(hk[kk], w[kk].y));
+          acc[j][2] = addf(acc[j][2], mulf(hk[kk], w[kk].z));
+          acc[j][3] = addf(acc[j][3], mulf(hk[kk], w[kk].w));
+        }
+      }
+    }
+  }
+
+  const int n0 = nb + 4 * tx;
+  if (n0 >= cl) return;
+#pragma unroll
+  for (int j = 0; j < RM; ++j) {
+    const int gr = rb + ty * RM + j;
+    if (gr >= Q) continue;
+    uint32_t key[4];
+#pragma unroll
+    for (int e = 0; e < 4; ++e) key[e] = orderable(-acc[j][e]);
+    // pitch % 64 == 0 and cl <= pitch: 16-B aligned, and the pad behind cl is this row's own
+    *reinterpret_cast<uint4 *>(keys + (int64_t)gr * pitch + n0) = make_uint4(key[0], key[1], key[2], key[3]);
+  }
+}
+
+// The LDS of one select (select_rows_kernel's).
+struct SelectLds {
+  uint32_t hist[1024];
+  int wtot[SNT / 64];
+  uint64_t prefix, mask;
+  int rem, done, cnt;
+  uint64_t sel[MAX_SEL];
+};
+
+// The `want` smallest of the composites item(0..count) that are not NONE, ascending in s.sel[0..want);
+// 1 <= want <= MAX_K and at most the number of such items.  id_max: no composite has a bit of its low
+// word above id_max's.  select_rows_kernel's radix select (10-bit digits from the top, windows split
+// at bit 32, stopping once the composites at or below the chosen bin fit the sort) and bitonic sort.
+template <class Item>
+__device__ __forceinline__ void select_smallest(SelectLds &s, const Item &item, int count, int want,
+                                                uint32_t id_max) {
+  const int tid = threadIdx.x;
+  int PN = 1;
+  while (PN < want) PN <<= 1;
+  const int limit = min(MAX_SEL, 2 * PN);
+  if (tid == 0) {
+    s.prefix = 0;
+    s.mask = 0;
+    s.rem = want;
+    s.done = 0;
+    s.cnt = 0;
+  }
+  __syncthreads();
+  for (int pass = 0; pass < 8; ++pass) {
+    const int shift = pass < 3 ? 54 - 10 * pass : pass == 3 ? 32 : pass < 7 ? 22 - 10 * (pass - 4) : 0;
+    const uint32_t dmask = (pass == 3 || pass == 7) ? 3u : 1023u;
+    if (shift < 32 && (id_max >> shift) == 0u) continue;  // no id has a bit up here
+    if (s.done) break;
+    const uint64_t prefix = s.prefix, mask = s.mask;
+    const int rem = s.rem;
+    s.hist[tid] = 0u;
+    __syncthreads();
+    for (int j = tid; j < count; j += SNT) {
+      const uint64_t cmp = item(j);
+      if (cmp != NONE && (cmp & mask) == prefix) atomicAdd(&s.hist[(uint32_t)(cmp >> shift) & dmask], 1u);
+    }
+    __syncthreads();
+    // thread t owns bin t: its inclusive scan is the count of matching items in bins <= it
+    const int v = (int)s.hist[tid];
+    const int le = rowsort::block_incl_scan<SNT>(v, s.wtot), lt = le - v;
+    if (le >= rem && lt < rem) {  // exactly one bin: the one holding the rem-th smallest
+      s.prefix = prefix | ((uint64_t)tid << shift);
+      s.mask = mask | ((uint64_t)dmask << shift);
+      s.rem = rem - lt;
+      s.done = (want - (rem - lt)) + v <= limit;  // everything at or below this bin: want or a few more
+    }
+    __syncthreads();
+  }
+  // the bits outside the mask are below every decided digit or zero in every composite: on the
+  // decided bits, a candidate <=> at or below the prefix; all passes done, exactly `want` of them
+  const uint64_t T = s.prefix, M = s.mask;
+  for (int j = tid; j < count; j += SNT) {
+    const uint64_t cmp = item(j);
+    if (cmp != NONE && (cmp & M) <= T) {
+      const int pos = atomicAdd(&s.cnt, 1);
+      if (pos < limit) s.sel[pos] = cmp;
+    }
+  }
+  __syncthreads();
+  const int cnt = min(s.cnt, limit);  // (want <= cnt <= limit by the counts; never past sel)
+  int P = PN;
+  while (P < cnt) P <<= 1;
+  for (int i = cnt + tid; i < P; i += SNT) s.sel[i] = NONE;
+  __syncthreads();
+  rowsort::bitonic_sort<SNT>(P, rowsort::CmpSwapU64<false>{s.sel});
+}
+
+struct ChunkItem {  // key << 32 | cube position inside the chunk; the skipped cube is no candidate
+  const uint32_t *k;
+  int skip;
+  __device__ __forceinline__ uint64_t operator()(int j) const {
+    const uint64_t cmp = ((uint64_t)k[j] << 32) | (uint32_t)j;  // loaded whatever j: no branch
+    return j == skip ? NONE : cmp;
+  }
+};
+struct CandItem {
+  const uint64_t *c;
+  __device__ __forceinline__ uint64_t operator()(int j) const { return c[j]; }
+};
+
+// The first `want` entries of s.sel as a result row, then the -1 / 0.f tail.
+__device__ __forceinline__ void write_row(const SelectLds &s, int want, int k, int32_t *oi, float *od) {
+  for (int i = threadIdx.x; i < want; i += SNT) {
+    const uint64_t cmp = s.sel[i];
+    oi[i] = (int32_t)(uint32_t)cmp;
+    od[i] = dist_of_key((uint32_t)(cmp >> 32));
+  }
+  for (int i = max(want, 0) + threadIdx.x; i < k; i += SNT) {
+    oi[i] = -1;
+    od[i] = 0.f;
+  }
+}
+
+// The select kernels are held to 80 allocated SGPRs (72 and the 6 the hardware adds, in steps of
+// 16): at 96 a CU takes one 1,024-thread workgroup instead of two, and these loops, one load in
+// flight per lane, then run 1.4 times as long (measured: 184 against 129 us).
+#define CUBESIM_SELECT_KERNEL __attribute__((amdgpu_num_sgpr(72))) __global__ __launch_bounds__(SNT)
+
+// Candidates of (query r, this chunk): cand[r][chunk][0..k), global cube ids, NONE behind the last.
+// FINAL (the corpus is one chunk): the chunk's candidates are the row's result, written as such.
+template <bool FINAL>
+CUBESIM_SELECT_KERNEL void select_chunk_kernel(const uint32_t *__restrict__ keys, int pitch, int c0, int cl,
+                                               const int32_t *__restrict__ qok,
+                                               const int32_t *__restrict__ skip, int k, int chunk_no,
+                                               int chunks, uint64_t *__restrict__ cand,
+                                               int32_t *__restrict__ out_idx, float *__restrict__ out_dist) {
+  __shared__ SelectLds s;
+  const int tid = threadIdx.x;
+  const int r = blockIdx.x;
+  int want = 0;
+  if (qok[r]) {  // (block-uniform)
+    const int sk = skip ? skip[r] : -1;
+    const int skl = (sk >= c0 && sk < c0 + cl) ? sk - c0 : -1;  // inside this chunk: its position
+    want = min(k, cl - (skl >= 0 ? 1 : 0));
+    if (want > 0) select_smallest(s, ChunkItem{keys + (int64_t)r * pitch, skl}, cl, want, (uint32_t)(cl - 1));
+  } else if (!FINAL) {
+    return;  // the merge reads nothing of a row that is no query
+  }
+  if (FINAL) {
+    write_row(s, want, k, out_idx + (int64_t)r * k, out_dist + (int64_t)r * k);  // c0 == 0
+  } else {
+    uint64_t *out = cand + ((int64_t)r * chunks + chunk_no) * k;
+    // c0 + position < 2^31: the sum stays inside the low word
+    for (int i = tid; i < want; i += SNT) out[i] = s.sel[i] + (uint32_t)c0;
+    for (int i = max(want, 0) + tid; i < k; i += SNT) out[i] = NONE;
+  }
+}
+
+CUBESIM_SELECT_KERNEL void merge_rows_kernel(const uint64_t *__restrict__ cand, int chunks,
+                                                         int N, const int32_t *__restrict__ qok,
+                                                         const int32_t *__restrict__ skip, int k,
+                                                         int32_t *__restrict__ out_idx,
+                                                         float *__restrict__ out_dist) {
+  __shared__ SelectLds s;
+  const int tid = threadIdx.x;
+  const int r = blockIdx.x;
+  int32_t *oi = out_idx + (int64_t)r * k;
+  float *od = out_dist + (int64_t)r * k;
+  int want = 0;
+  if (qok[r]) {  // (block-uniform)
+    const int sk = skip ? skip[r] : -1;
+    want = min(k, N - ((uint32_t)sk < (uint32_t)N ? 1 : 0));
+  }
+  // chunks * k stays below 2^31: larger counts are refused by the entry
+  if (want > 0) select_smallest(s, CandItem{cand + (int64_t)r * chunks * k}, chunks * k, want, (uint32_t)(N - 1));
+  write_row(s, want, k, oi, od);
+}
+
+int k_pad(int K) { return (int)cdiv(std::max(K, 1), KS) * KS; }
+int cap_pitch(int cap) { return (int)cdiv(std::max(cap, 1), 64) * 64; }
+
+// index: [n cap*Kp][nT Kp*caps]
+struct IndexLayout {
+  size_t n, nT, total;
+  int Kp, caps;
+};
+IndexLayout index_layout(int cap, int K) {
+  IndexLayout x;
+  x.Kp = k_pad(K);
+  x.caps = cap_pitch(cap);
+  size_t o = 0;
+  x.n = o, o += align256((size_t)std::max(cap, 1) * x.Kp * sizeof(float));
+  x.nT = o, o += align256((size_t)x.Kp * x.caps * sizeof(float));
+  x.total = o;
+  return x;
+}
+
+// workspace: [keys Q*pitch][cand Q*chunks*k][qn Q*Kp][qok Q], pitch = the chunk, or N rounded up to
+// 64 where that is less: it grows with Q * chunk and Q * k * chunks, never with Q * N
+struct SearchWs {
+  size_t qn, qok, keys, cand, total;
+  int Kp, chunk, pitch, chunks;
+};
+SearchWs search_ws(int N, int K, int Q, int k, int chunk) {
+  SearchWs w;
+  const size_t q = (size_t)std::max(Q, 1), n = (size_t)std::max(N, 1);
+  w.Kp = k_pad(K);
+  w.chunk = chunk > 0 ? chunk : DEFAULT_CHUNK;
+  w.pitch = (int)std::min<size_t>((size_t)w.chunk, (size_t)cdiv((int64_t)n, 64) * 64);
+  w.chunks = (int)cdiv((int64_t)n, w.chunk);
+  size_t o = 0;
+  w.keys = o, o += align256(q * w.pitch * sizeof(uint32_t));
+  w.cand = o, o += align256(q * (size_t)w.chunks * (size_t)std::max(k, 1) * sizeof(uint64_t));
+  w.qn = o, o += align256(q * w.Kp * sizeof(float));
+  w.qok = o, o += align256(q * sizeof(int32_t));
+  w.total = o;
+  return w;
+}
+
+template <int RM>
+void launch_dist(hipStream_t s, const float *qn, const int32_t *qok, const float *nT, int caps, int c0,
+                 int cl, int Kp, int Q, int pitch, uint32_t *keys) {
+  const dim3 grid((unsigned)cdiv(cl, TC), (unsigned)cdiv(Q, 16 * RM));
+  hipLaunchKernelGGL(dist_chunk_kernel<RM>, grid, dim3(DNT), 0, s, qn, qok, nT, caps, c0, cl, Kp, Q, pitch,
+                     keys);
+}
+
+}  // namespace
+
+extern "C" size_t cc_cube_index_size(int32_t cap, int32_t K) { return index_layout(cap, K).total; }
+
+extern "C" int cc_cube_index_put(void *index, int32_t cap, int32_t K, int32_t n0, int32_t rows,
+                                 const float *z, void *stream) {
+  CC_REQUIRE(index && z, "cc_cube_index_put: null pointer");
+  CC_REQUIRE(((uintptr_t)index & 255) == 0, "cc_cube_index_put: index must be 256-byte aligned");
+  CC_REQUIRE(cap >= 1 && cap <= 0x7FFFFFFF - 64 && K >= 1 && K <= 0x7FFFFFFF - KS,
+             "cc_cube_index_put: bad cap/K");
+  CC_REQUIRE(n0 >= 0 && rows >= 0 && (int64_t)n0 + rows <= cap,
+             "cc_cube_index_put: rows [n0, n0 + rows) must lie inside [0, cap)");
+  if (rows == 0) return CC_OK;
+  const IndexLayout x = index_layout(cap, K);
+  char *base = (char *)index;
+  hipLaunchKernelGGL(put_rows_kernel, dim3((unsigned)cdiv(rows, NR)), dim3(NR), 0, as_stream(stream), z,
+                     rows, K, x.Kp, x.caps, n0, (float *)(base + x.n), (float *)(base + x.nT));
+  CC_LAUNCH_CHECK("put_rows_kernel");
+  return CC_OK;
+}
+
+extern "C" int32_t cc_cube_neighbours_max_k(void) { return MAX_K; }
+
+extern "C" size_t cc_cube_neighbours_ws_size(int32_t N, int32_t K, int32_t Q, int32_t k, int32_t chunk) {
+  return search_ws(N, K, Q, k, chunk).total + 256;
+}
+
+extern "C" int cc_cube_neighbours(const void *index, int32_t cap, int32_t N, int32_t K, int32_t Q,
+                                  const int32_t *qid, const float *zq, const int32_t *skip, int32_t k,
+                                  int32_t chunk, void *ws, int32_t *out_idx, float *out_dist,
+                                  void *stream) {
+  CC_REQUIRE(index && ws && out_idx && out_dist, "cc_cube_neighbours: null pointer");
+  CC_REQUIRE(cap >= 1 && cap <= 0x7FFFFFFF - 64 && K >= 1 && K <= 0x7FFFFFFF - KS,
+             "cc_cube_neighbours: bad cap/K");
+  CC_REQUIRE(N >= 1 && N <= cap, "cc_cube_neighbours: N must be 1..cap");
+  CC_REQUIRE(Q >= 0 && Q <= MAX_Q, "cc_cube_neighbours: Q outside 0..2^22");
+  CC_REQUIRE(k >= 1 && k <= MAX_K, "cc_cube_neighbours: k must be 1..cc_cube_neighbours_max_k()");
+  CC_REQUIRE(chunk == 0 || (chunk > 0 && chunk % 64 == 0),
+             "cc_cube_neighbours: chunk must be 0 or a positive multiple of 64");
+  CC_REQUIRE(((uintptr_t)ws & 255) == 0, "cc_cube_neighbours: ws must be 256-byte aligned");
+  CC_REQUIRE(((uintptr_t)index & 255) == 0, "cc_cube_neighbours: index must be 256-byte aligned");
+  const SearchWs w = search_ws(N, K, Q, k, chunk);
+  CC_REQUIRE((int64_t)w.chunks * k <= 0x7FFFFFFF, "cc_cube_neighbours: k * chunks above 2^31 - 1, use a larger chunk");
+  if (Q == 0) return CC_OK;
+  const IndexLayout x = index_layout(cap, K);
+  hipStream_t s = as_stream(stream);
+  const float *n = (const float *)((const char *)index + x.n);
+  const float *nT = (const float *)((const char *)index + x.nT);
+  char *base = (char *)ws;
+  float *qn = (float *)(base + w.qn);
+  int32_t *qok = (int32_t *)(base + w.qok);
+  uint32_t *keys = (uint32_t *)(base + w.keys);
+  uint64_t *cand = (uint64_t *)(base + w.cand);
+  hipLaunchKernelGGL(query_rows_kernel, dim3(Q), dim3(QNT), 0, s, n, N, K, x.Kp, qid, zq, qn, qok);
+  CC_LAUNCH_CHECK("query_rows_kernel");
+  const bool one_chunk = w.chunks == 1;  // its select writes the rows: no merge
+  for (int c = 0; c < w.chunks; ++c) {
+    const int c0 = (int)((int64_t)c * w.chunk), cl = std::min(w.chunk, N - c0);
+    // queries per tile: 32 / 64 / 128 (the arithmetic per (query, cube) does not depend on it)
+    if (Q <= 32)
+      launch_dist<2>(s, qn, qok, nT, x.caps, c0, cl, x.Kp, Q, w.pitch, keys);
+    else if (Q <= 64)
+      launch_dist<4>(s, qn, qok, nT, x.caps, c0, cl, x.Kp, Q, w.pitch, keys);
+    else
+      launch_dist<8>(s, qn, qok, nT, x.caps, c0, cl, x.Kp, Q, w.pitch, keys);
+    CC_LAUNCH_CHECK("dist_chunk_kernel");
+    if (one_chunk)
+      hipLaunchKernelGGL(select_chunk_kernel<true>, dim3(Q), dim3(SNT), 0, s, keys, w.pitch, c0, cl, qok, skip,
+                         k, c, w.chunks, cand, out_idx, out_dist);
+    else
+      hipLaunchKernelGGL(select_chunk_kernel<false>, dim3(Q), dim3(SNT), 0, s, keys, w.pitch, c0, cl, qok, skip,
+                         k, c, w.chunks, cand, out_idx, out_dist);
+    CC_LAUNCH_CHECK("select_chunk_kernel");
+  }
+  if (!one_chunk) {
+    hipLaunchKernelGGL(merge_rows_kernel, dim3(Q), dim3(SNT), 0, s, cand, w.chunks, N, qok, skip, k, out_idx,
+                       out_dist);
+    CC_LAUNCH_CHECK("merge_rows_kernel");
+  }
+  return CC_OK;
+}

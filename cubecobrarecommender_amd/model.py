@@ -279,6 +279,12 @@ class CC_Recommender:
         """The resident single-cube recommend engine (fp32 forward + GPU top-N)."""
         return self._rec()
 
+    def cube_index(self, cubes, capacity=None):
+        """A resident index of `cubes` (card-index lists) under the current weights' encoder, for
+        "cubes like this one": cubesim.CubeIndex (neighbours, neighbours_of, table, add)."""
+        from .cubesim import CubeIndex
+        return CubeIndex(self.recommender(), cubes, capacity=capacity)
+
     def evaluate_holdout(self, cubes, **kw):
         """Held-out ranking metrics (recall@K, NDCG@K, hit rate@K, MRR) of the current weights on
         `cubes` (card-index lists): evaluate.evaluate_holdout through the resident recommender."""

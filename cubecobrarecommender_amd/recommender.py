@@ -263,6 +263,12 @@ class Recommender:
         self.stream.synchronize()
         return out
 
+    def cube_index(self, cubes, capacity=None):
+        """A resident index of `cubes` (card-index lists) for nearest-cube searches
+        (cubesim.CubeIndex)."""
+        from .cubesim import CubeIndex
+        return CubeIndex(self, cubes, capacity=capacity)
+
     # ------------------------------------------------------------------ card pools
     def card_pool(self, ids):
         """A CardPool of `ids` for this model with its bit row on the device: uploaded once, then

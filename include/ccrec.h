@@ -694,6 +694,37 @@ int cc_similar_cards_batch_timed(const float *emb, int32_t V, int32_t K, int32_t
                                  float *out_dist, float *dist_all, float *kernel_ms, void *stream);
 
 /* ----------------------------------------------------------------------------------
+ * Similar cubes: a resident index of cube embeddings (the encoder's [K]-float latent of a whole
+ * cube, cc_infer_encode_fp32) and the exact k nearest cubes of Q queries over it, in card
+ * similarity's pinned arithmetic (above) and order: ascending distance, equal distances lower cube
+ * id first.  The index is opaque, caller-owned, 256-byte aligned, cc_cube_index_size(cap, K) bytes
+ * for up to cap cubes; it is normalised once, by the puts, and never by a search.
+ *   cc_cube_index_put: normalises raw embeddings z [rows][K] (device) into index rows
+ *     [n0, n0 + rows), any n0 and rows inside [0, cap).  Puts that cover [0, N), in any order and
+ *     any pieces, leave what one put of all N rows leaves; the pads of a row are written with it.
+ *     rows == 0 returns CC_OK and launches nothing.
+ *   cc_cube_neighbours: query r is index row qid[r] when 0 <= qid[r] < N; the raw embedding
+ *     zq[r][0..K) (normalised by the put's arithmetic) when qid[r] < 0 or qid == NULL, and
+ *     zq != NULL; anything else is never used as an index and gives a row of -1 / 0.f.  skip: NULL
+ *     or [Q]; cube skip[r] is left out of row r's candidates, a value outside [0, N) leaves out
+ *     nothing.  out_idx / out_dist [Q][k]: the first min(k, candidates of the row) entries in rank
+ *     order, then -1 / 0.f; a zero distance is -0.0f.  1 <= k <= cc_cube_neighbours_max_k().
+ *     chunk: corpus cubes per pass, 0 for the default, else a positive multiple of 64; no output
+ *     bit depends on it.  Only rows [0, N) of the index are read.  ws:
+ *     cc_cube_neighbours_ws_size(N, K, Q, k, chunk) bytes, 256-byte aligned: Q * min(chunk, N)
+ *     sort keys and Q * k * ceil(N / chunk) candidates, never Q * N; nothing in it is assumed to
+ *     survive from an earlier call.  Q == 0 returns CC_OK and launches nothing.
+ * ---------------------------------------------------------------------------------- */
+size_t cc_cube_index_size(int32_t cap, int32_t K);
+int cc_cube_index_put(void *index, int32_t cap, int32_t K, int32_t n0, int32_t rows, const float *z,
+                      void *stream);
+int32_t cc_cube_neighbours_max_k(void);
+size_t cc_cube_neighbours_ws_size(int32_t N, int32_t K, int32_t Q, int32_t k, int32_t chunk);
+int cc_cube_neighbours(const void *index, int32_t cap, int32_t N, int32_t K, int32_t Q,
+                       const int32_t *qid, const float *zq, const int32_t *skip, int32_t k,
+                       int32_t chunk, void *ws, int32_t *out_idx, float *out_dist, void *stream);
+
+/* ----------------------------------------------------------------------------------
  * Top-N (ml_recommend.py:87-108): rank all V probabilities descending, ties -> higher
  * index first (= numpy argsort(kind='stable')[::-1]); additions = first max(amount,1)
  * indices not in the cube; cut_vals[i] = probs[cube_idx[i]].  cube_idx: n DISTINCT card ids.
