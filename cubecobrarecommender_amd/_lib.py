@@ -229,7 +229,10 @@ SIGNATURES = {
                                                             _P, _P, _P, _P, _P, _P, _P, _I32, _P, _P]),
     'cc_recommend_batch_loss_ws_size': (_SZ, [_I32, _I32, _I32, _I32]),
     'cc_recommend_batch_loss_fp32': (C.c_int, [_P, _I32, _I32, _I32, _P, _P, _I32, _P, _P, _P, _P, _P, _P]),
-    'cc_adjacency_ws_size': (_SZ, [_I32, _I32, _I32, _I32]),
+    'cc_leave_one_out_ws_size': (_SZ, [_I32, _I32, _I32, _I32, _I32]),
+    'cc_leave_one_out_fp32': (C.c_int, [_P, _I32, _I32, _I32, _P, _P, _I32, _I32, _P, _P, _P, _P, _P, _P, _P, _SZ,
+                                        _P]),
+    'cc_adjacency_ws_size':(_SZ, [_I32, _I32, _I32, _I32]),
     'cc_adjacency': (C.c_int, [_P, _P, _I32, _I32, _I32, _P, _P, _P, _P, _P, _P]),
     'cc_graph_rec_max_amount': (_I32, []),
     'cc_graph_rec_ws_size': (_SZ, [_I32, _I32, _I32]),

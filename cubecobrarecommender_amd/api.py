@@ -98,6 +98,37 @@ def similar_cubes(index, cube_indices, k, cube_names=None):
             for i, (j, dv) in enumerate(zip(idx[0], dists[0]))]
 
 
+def leave_one_out_cuts(model, cube_indices, int_to_card):
+    """Honest cut values of one cube: {name: (with, without)} with `with` = p(c | cube), the value
+    `recommend` reports under "cuts", and `without` = p(c | cube without c)
+    (Recommender.leave_one_out).  Ordered first cut first: `without` ascending, equal values lower
+    card id first."""
+    ids = np.asarray(list(cube_indices), np.int64).reshape(-1)
+    out = model.recommender().leave_one_out([ids])[0]
+    result = {}
+    for i in np.lexsort((ids, out['loo_vals'])).tolist():
+        result.setdefault(int_to_card[int(ids[i])], (float(out['cut_vals'][i]), float(out['loo_vals'][i])))
+    return result
+
+
+def explain(model, cube_indices, target_ids, int_to_card, top=10):
+    """Why was a card recommended?  {target name: {"base": p(t | cube), "cards": [(name, gain)]}}
+    with gain = p(t | cube) - p(t | cube without c) (a float32 subtraction) for the `top` distinct
+    cube cards c with the largest gain, largest first, equal gains lower card id first."""
+    ids = np.asarray(list(cube_indices), np.int64).reshape(-1)
+    tgt = np.asarray(list(target_ids), np.int64).reshape(-1)
+    out = model.recommender().leave_one_out([ids], targets=[tgt])[0]
+    cards, first = np.unique(ids, return_index=True)
+    result = {}
+    for t, card in enumerate(tgt.tolist()):
+        base = np.float32(out['base'][t])
+        gain = (base - out['without'][first, t]).astype(np.float32)
+        best = np.lexsort((cards, -gain))[:max(int(top), 0)]
+        result[int_to_card[card]] = {'base': float(base),
+                                     'cards': [(int_to_card[int(cards[i])], float(gain[i])) for i in best.tolist()]}
+    return result
+
+
 def _graph_of(adj_mtx):
     """adj_mtx as a GraphRecommender: one passed in is used as it is (its graph stays resident);
     a matrix is uploaded for this call."""

@@ -317,6 +317,20 @@ int infer_h3_launch(const float *params, int V, int d, int R, const int32_t *row
   CC_LAUNCH_CHECK("tower_kernel(batch)");
   return CC_OK;
 }
+
+// Both towers for R rows whose E1 totals are ready (loo.hip): e1 [R][d] is read as one-chunk
+// partials (cap = 1) under one_ptr [R + 1] = 0 .. R, the CSR of rows of one card each.  0 + x is
+// exact and a total summed from +0 is never -0, so the rows are the towers' of those totals.
+int infer_towers_launch(const float *params, int V, int d, int R, const int32_t *one_ptr,
+                        const float *e1, float *zlat, float *h3, hipStream_t s) {
+  Tower T;
+  if (int rc = make_tower(params, V, d, T)) return rc;
+  const tiles::Req none{nullptr, nullptr, 0, 0};
+  hipLaunchKernelGGL(tower_kernel, dim3(R), dim3(NT), tower_lds_bytes(d), s, T, 2, one_ptr, none,
+                     (uint32_t *)nullptr, e1, 1, (const float *)nullptr, zlat, h3);
+  CC_LAUNCH_CHECK("tower_kernel(totals)");
+  return CC_OK;
+}
 }  // namespace cc
 
 // ---------------------------------------------------------------------- single-cube request

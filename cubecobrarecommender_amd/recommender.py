@@ -520,6 +520,25 @@ class Recommender:
             pipelined(row_spans(R, rows_per_launch), launch, collect)
         return row_loss, row_pred
 
+    # ------------------------------------------------------------------ leave-one-out scores
+    def leave_one_out(self, cubes, targets=None, rows_per_launch=4096):
+        """p(card | cube without c) for every card c of every cube (cc_leave_one_out_fp32): each
+        value is, bit for bit, what `recommend_many` gives for the cube with c taken out, but the
+        E1 chunk sums are shared between a cube's rows and the output layer runs at the wanted
+        cards only.  Launches hold up to rows_per_launch derived rows (a cube of n distinct cards
+        has n + 1); a larger cube is sliced by positions.  Returns one dict per cube.
+
+        targets=None: loo_vals, p(c | cube without c), and cut_vals, p(c | cube) as
+        `recommend_many` returns it; both float32 [m] in the cube's input order, duplicated ids
+        repeating their value.
+        targets: one list of card ids per cube, or one flat list for every cube; base float32 [T]
+        is p(t | cube) and without float32 [m, T] is p(t | cube without the card of input entry
+        i), in the order given.  A target may be a cube card and may be the card left out.  More
+        results than the staging budget holds are split by targets as well as by rows.
+        An id outside [0, V) in either argument raises ValueError before anything is launched."""
+        from .leaveoneout import leave_one_out
+        return leave_one_out(self, cubes, targets, rows_per_launch)
+
     def _full_order(self, probs, uniq, amount):
         """The complete ranking (cc_topn with `order`; tests and tools only)."""
         V, dev = self.V, self.dev

@@ -889,6 +889,35 @@ int cc_recommend_batch_loss_fp32(const float *params, int32_t V, int32_t d, int3
                                  const int32_t *tgt_ptr, const int32_t *tgt, void *ws,
                                  double *row_loss, int32_t *row_pred, void *stream);
 
+/* Leave-one-out scores: p(card | cube without c), each derived row bit-identical to the forward
+ * pass of cc_recommend_batch_fp32 on the shorter list.
+ *   row_ptr [n_cubes + 1], idx, max_n: the cubes' CSR with the PRECONDITIONS of
+ *   cc_recommend_batch_fp32 (sorted distinct ids in [0, V)).
+ *   rows derived rows: row r is cube row_cube[r] without the id at sorted position row_pos[r];
+ *   row_pos[r] == -1 leaves nothing out (the base row: the plain forward pass).  A row whose cube
+ *   is outside [0, n_cubes) or whose position is outside [-1, n) is never used as an index and
+ *   writes nothing; an id outside [0, V) is never used as an index either.
+ *   out_ptr [rows + 1]: row r's results are out[out_ptr[r] .. out_ptr[r + 1]); a row never writes
+ *   more words than that.
+ *   tgt_ptr [n_cubes + 1], tgt: CSR of target cards per CUBE (device), any order, duplicates and
+ *   cube cards allowed: every row of the cube gets T = tgt_ptr[c + 1] - tgt_ptr[c] probabilities,
+ *   in target order; a target outside [0, V) gets 0.f.
+ *   tgt_ptr == NULL (self mode): a derived row gets ONE word, the probability of its left-out
+ *   card; a base row gets n words, the cube cards' probabilities aligned with idx (the cut_vals
+ *   of cc_recommend_batch_fp32).  Nothing of size n x n is computed or written.
+ *   ws: ws_bytes >= cc_leave_one_out_ws_size(V, d, n_cubes, max_n, rows) bytes, 256-B aligned:
+ *   2 * n_cubes * max(1, ceil(max_n / 32)) * d floats of chunk partials and rows * (2 d + 64) + rows
+ *   + 1 words per launch; the call does not depend on its contents.  rows == 0 returns CC_OK
+ *   without a launch.
+ * CC_ERR_ARG: null pointer (tgt may be NULL only with tgt_ptr NULL), max_n > V, d not a multiple of
+ * 64 in [64, 1024], unaligned or undersized ws, rows > 0 with n_cubes == 0; nothing is launched. */
+size_t cc_leave_one_out_ws_size(int32_t V, int32_t d, int32_t n_cubes, int32_t max_n, int32_t rows);
+int cc_leave_one_out_fp32(const float *params, int32_t V, int32_t d, int32_t n_cubes,
+                          const int32_t *row_ptr, const int32_t *idx, int32_t max_n, int32_t rows,
+                          const int32_t *row_cube, const int32_t *row_pos, const int32_t *tgt_ptr,
+                          const int32_t *tgt, const int32_t *out_ptr, float *out, void *ws,
+                          size_t ws_bytes, void *stream);
+
 /* ---------------------------------------------------------------- card co-occurrence graph (N1)
  * Replaces src/non_ml/utils.py:75-91 (create_adjacency_matrix, called by
  * src/non_ml/create_mtx.py:19) and the M~ normalisation of src/ml/train.py:69-71.
