@@ -232,6 +232,10 @@ SIGNATURES = {
     'cc_leave_one_out_ws_size': (_SZ, [_I32, _I32, _I32, _I32, _I32]),
     'cc_leave_one_out_fp32': (C.c_int, [_P, _I32, _I32, _I32, _P, _P, _I32, _I32, _P, _P, _P, _P, _P, _P, _P, _SZ,
                                         _P]),
+    'cc_complete_max_per_step': (_I32, []),
+    'cc_complete_ws_size': (_SZ, [_I32, _I32, _I32, _I32, _I32]),
+    'cc_complete_fp32': (C.c_int, [_P, _I32, _I32, _I32, _P, _P, _I32, _P, _I32, _I32, _P, _I32, _P, _I32, _P, _P,
+                                   _P, _P, _SZ, _P]),
     'cc_adjacency_ws_size':(_SZ, [_I32, _I32, _I32, _I32]),
     'cc_adjacency': (C.c_int, [_P, _P, _I32, _I32, _I32, _P, _P, _P, _P, _P, _P]),
     'cc_graph_rec_max_amount': (_I32, []),

@@ -111,6 +111,14 @@ def leave_one_out_cuts(model, cube_indices, int_to_card):
     return result
 
 
+def complete_cube(model, cube_indices, size, int_to_card, pool=None, per_step=1):
+    """Fill one cube up to `size` cards (Recommender.complete): {"additions": {name: p}} in the
+    order the cards were picked, p the probability a card had in the pass that picked it.
+    per_step=1 re-scores the cube after every card; pool: a CardPool the cards come from."""
+    out = model.recommender().complete(list(cube_indices), size, per_step=per_step, pool=pool)
+    return {'additions': {int_to_card[idx]: p for idx, p in zip(out['added'].tolist(), out['added_vals'].tolist())}}
+
+
 def explain(model, cube_indices, target_ids, int_to_card, top=10):
     """Why was a card recommended?  {target name: {"base": p(t | cube), "cards": [(name, gain)]}}
     with gain = p(t | cube) - p(t | cube without c) (a float32 subtraction) for the `top` distinct

@@ -39,6 +39,8 @@
 //   out_tile_kernel<RM, true> takes the key from the exclusion word and the cut-value search from
 //                     the cube word; topn_rows_kernel<true> / rank_rows_kernel<true> take want from
 //                     n_cand[r] instead of V - n; target_ranks_kernel is fed the pooled keys.
+// cc::batch_select_launch is the select chain (keys + topn_rows_kernel, pooled or not) as
+// complete.hip runs it pass after pass; the two select entries are that call behind their checks.
 #include "common.hpp"
 #include "detmath.hpp"
 #include "rowsort.hpp"
@@ -660,6 +662,46 @@ static int pools_check(const std::string &who, const uint32_t *pools, int n_pool
   return CC_OK;
 }
 
+// ---------------------------------------------------------------------- pieces for complete.hip
+namespace cc {
+int batch_max_amount() { return MAX_AMOUNT; }
+
+// bytes of workspace batch_select_launch uses (pooled: with the pools' share)
+size_t batch_select_ws_bytes(int V, int d, int R, int max_n, bool pooled) {
+  const BatchWs w = batch_ws(V, d, R, max_n);
+  return pooled ? pool_ws(w, R).total : w.total;
+}
+
+// The chain behind cc_recommend_batch_fp32 (pool_of_row null) and cc_recommend_batch_pool_fp32:
+// keys, then the select of every row's first max(amount, 1) candidates; the row pitch of
+// additions / add_vals is max(amount, 1).  The arguments are the entries', already checked; R > 0.
+int batch_select_launch(const float *params, int V, int d, int R, const int32_t *row_ptr,
+                        const int32_t *idx, int max_n, int amount, void *ws, int32_t *n_add,
+                        int32_t *additions, float *add_vals, float *cut_vals, float *probs,
+                        const uint32_t *pools, int n_pools, const int32_t *pool_of_row,
+                        hipStream_t s) {
+  const BatchWs w = batch_ws(V, d, R, max_n);
+  const uint32_t *keys = (const uint32_t *)((char *)ws + w.keys);
+  const int A = amount > 0 ? amount : 1;
+  if (!pool_of_row) {
+    if (int rc = batch_keys_launch(params, V, d, R, row_ptr, idx, max_n, ws, w, cut_vals, probs, s))
+      return rc;
+    hipLaunchKernelGGL(topn_rows_kernel<false>, dim3(R), dim3(SNT), 0, s, keys, w.Vs, V, row_ptr,
+                       amount, A, n_add, additions, add_vals, (const int32_t *)nullptr);
+  } else {
+    const Pools pl{pools, n_pools, pool_of_row};
+    const int32_t *n_cand = nullptr;
+    if (int rc = batch_keys_launch(params, V, d, R, row_ptr, idx, max_n, ws, w, cut_vals, probs, s,
+                                   &pl, &n_cand))
+      return rc;
+    hipLaunchKernelGGL(topn_rows_kernel<true>, dim3(R), dim3(SNT), 0, s, keys, w.Vs, V, row_ptr,
+                       amount, A, n_add, additions, add_vals, n_cand);
+  }
+  CC_LAUNCH_CHECK("topn_rows_kernel");
+  return CC_OK;
+}
+}  // namespace cc
+
 extern "C" int cc_recommend_batch_fp32(const float *params, int32_t V, int32_t d, int32_t R,
                                        const int32_t *row_ptr, const int32_t *idx, int32_t max_n,
                                        int32_t amount, void *ws, int32_t *n_add,
@@ -673,16 +715,8 @@ extern "C" int cc_recommend_batch_fp32(const float *params, int32_t V, int32_t d
              "cc_recommend_batch_fp32: amount above cc_recommend_batch_max_amount()");
   CC_REQUIRE(((uintptr_t)ws & 255) == 0, "cc_recommend_batch_fp32: ws must be 256-byte aligned");
   if (R == 0) return CC_OK;
-  const BatchWs w = batch_ws(V, d, R, max_n);
-  hipStream_t s = as_stream(stream);
-  if (int rc = batch_keys_launch(params, V, d, R, row_ptr, idx, max_n, ws, w, cut_vals, probs, s))
-    return rc;
-  const int A = amount > 0 ? amount : 1;
-  hipLaunchKernelGGL(topn_rows_kernel<false>, dim3(R), dim3(SNT), 0, s,
-                     (const uint32_t *)((char *)ws + w.keys), w.Vs, V, row_ptr, amount, A, n_add,
-                     additions, add_vals, (const int32_t *)nullptr);
-  CC_LAUNCH_CHECK("topn_rows_kernel");
-  return CC_OK;
+  return cc::batch_select_launch(params, V, d, R, row_ptr, idx, max_n, amount, ws, n_add, additions,
+                                 add_vals, cut_vals, probs, nullptr, 0, nullptr, as_stream(stream));
 }
 
 extern "C" size_t cc_recommend_batch_pool_ws_size(int32_t V, int32_t d, int32_t R, int32_t max_n) {
@@ -707,19 +741,9 @@ extern "C" int cc_recommend_batch_pool_fp32(const float *params, int32_t V, int3
   CC_REQUIRE(((uintptr_t)ws & 255) == 0,
              "cc_recommend_batch_pool_fp32: ws must be 256-byte aligned");
   if (R == 0) return CC_OK;
-  const BatchWs w = batch_ws(V, d, R, max_n);
-  hipStream_t s = as_stream(stream);
-  const Pools pl{pools, n_pools, pool_of_row};
-  const int32_t *n_cand = nullptr;
-  if (int rc = batch_keys_launch(params, V, d, R, row_ptr, idx, max_n, ws, w, cut_vals, probs, s,
-                                 &pl, &n_cand))
-    return rc;
-  const int A = amount > 0 ? amount : 1;
-  hipLaunchKernelGGL(topn_rows_kernel<true>, dim3(R), dim3(SNT), 0, s,
-                     (const uint32_t *)((char *)ws + w.keys), w.Vs, V, row_ptr, amount, A, n_add,
-                     additions, add_vals, n_cand);
-  CC_LAUNCH_CHECK("topn_rows_kernel");
-  return CC_OK;
+  return cc::batch_select_launch(params, V, d, R, row_ptr, idx, max_n, amount, ws, n_add, additions,
+                                 add_vals, cut_vals, probs, pools, n_pools, pool_of_row,
+                                 as_stream(stream));
 }
 
 // rank workspace: the batch workspace, then the two (key', card) ping-pong buffers [R][Vp] of

@@ -539,6 +539,28 @@ class Recommender:
         from .leaveoneout import leave_one_out
         return leave_one_out(self, cubes, targets, rows_per_launch)
 
+    # ------------------------------------------------------------------ greedy completion
+    def complete_many(self, cubes, sizes, per_step=1, pool=None, rows_per_launch=512):
+        """Fill every cube up to its size (cc_complete_fp32), bit for bit this loop per cube:
+        S = its sorted distinct ids; while len(S) < size: r = recommend(S, per_step, pool=pool);
+        take = r.additions[:size - len(S)]; stop if empty; S = sorted(S + take).  All passes of a
+        launch run on the device with no host round trip; launches hold up to rows_per_launch
+        cubes.  per_step=1 is exact greedy completion; a larger per_step (up to
+        cc_complete_max_per_step()) lets the top per_step cards join per forward pass.
+
+        sizes: one int for every cube or one per cube; a cube at or above its size gets nothing.
+        pool: as for recommend_many; a row ends early when its candidates run out.
+        Returns a list of {'added': int32 [k], 'added_vals': float32 [k]}: the cards in the order
+        they were picked and the probability each had in the pass that picked it.  The caller's
+        lists are not modified.  An id outside [0, V), a pool built for another V or another
+        number of sizes or pools raises ValueError before anything is launched."""
+        from .complete import complete_many
+        return complete_many(self, cubes, sizes, per_step, pool, rows_per_launch)
+
+    def complete(self, cube_indices, size, per_step=1, pool=None):
+        """`complete_many` for one cube: {'added', 'added_vals'}."""
+        return self.complete_many([cube_indices], size, per_step=per_step, pool=pool)[0]
+
     def _full_order(self, probs, uniq, amount):
         """The complete ranking (cc_topn with `order`; tests and tools only)."""
         V, dev = self.V, self.dev

@@ -918,6 +918,42 @@ int cc_leave_one_out_fp32(const float *params, int32_t V, int32_t d, int32_t n_c
                           const int32_t *tgt, const int32_t *out_ptr, float *out, void *ws,
                           size_t ws_bytes, void *stream);
 
+/* Greedy completion: fill R cubes up to a target size, `passes` forward passes in one stream of
+ * launches with no host round trip.  Row r with sorted ids S_r is defined by the loop
+ *   while |S_r| < target_n[r]:  picks = the additions of cc_recommend_batch_fp32 (or of
+ *   cc_recommend_batch_pool_fp32, with pools) on S_r at amount = per_step; take the first
+ *   min(|picks|, target_n[r] - |S_r|) of them, stop if there are none; append them and their
+ *   add_vals to the row's results; S_r = S_r + taken
+ * and every pick and value is bit for bit that loop's.  per_step == 1 is exact greedy completion.
+ *   row_ptr [R + 1], idx: the cubes' CSR with the PRECONDITIONS of cc_recommend_batch_fp32 (sorted
+ *   distinct ids in [0, V), row_ptr[0] == 0); neither is written.
+ *   target_n [R] (device): the size row r is filled to; at or below the row's length adds nothing.
+ *   max_n >= the longest row at any time: max over r of max(n_r, min(target_n[r], V)).  No row
+ *   grows beyond max_n.
+ *   per_step in [1, cc_complete_max_per_step()] (at least 256).
+ *   passes: forward passes to run; max over r of ceil((target_n[r] - n_r) / per_step) finishes
+ *   every row.  A finished or exhausted row is carried along unchanged, so more passes than needed
+ *   change nothing.
+ *   pools, n_pools, pool_of_row: as for cc_recommend_batch_pool_fp32; all three NULL / 0 / NULL is
+ *   the unpooled call.
+ *   n_added [R]; added / added_vals [R][A], A >= 1: row r's picks in the order taken and the
+ *   probability each had in the pass that took it, the unused tail -1 / 0.f.  A row never writes
+ *   past its A entries: A >= max over r of max(0, min(target_n[r], V) - n_r) holds them all.
+ *   ws: ws_bytes >= cc_complete_ws_size(V, d, R, max_n, per_step) bytes, 256-B aligned: the pooled
+ *   select workspace, two CSR buffers and one of cut values of R * max_n words each, and the
+ *   passes' picks; the call does not depend on its contents.  R == 0 or passes == 0 returns CC_OK
+ *   without a launch (and writes nothing).
+ * CC_ERR_ARG: null pointer, max_n > V, A < 1, d not a multiple of 64 in [64, 1024], per_step
+ * outside [1, cc_complete_max_per_step()], passes < 0, pool_of_row null with pools given, n_pools
+ * < 0, pools null with n_pools > 0, unaligned or undersized ws; nothing is launched. */
+int32_t cc_complete_max_per_step(void);
+size_t cc_complete_ws_size(int32_t V, int32_t d, int32_t R, int32_t max_n, int32_t per_step);
+int cc_complete_fp32(const float *params, int32_t V, int32_t d, int32_t R, const int32_t *row_ptr,
+                     const int32_t *idx, int32_t max_n, const int32_t *target_n, int32_t per_step,
+                     int32_t passes, const uint32_t *pools, int32_t n_pools,
+                     const int32_t *pool_of_row, int32_t A, int32_t *n_added, int32_t *added,
+                     float *added_vals, void *ws, size_t ws_bytes, void *stream);
+
 /* ---------------------------------------------------------------- card co-occurrence graph (N1)
  * Replaces src/non_ml/utils.py:75-91 (create_adjacency_matrix, called by
  * src/non_ml/create_mtx.py:19) and the M~ normalisation of src/ml/train.py:69-71.

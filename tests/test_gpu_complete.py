@@ -1,0 +1,337 @@
+"""Greedy completion on the device: Recommender.complete_many / complete, api.complete_cube and
+cc_complete_fp32 itself.  The definition is the host loop of tests/complete_ref.py over the existing
+single requests; everything is np.array_equal on ids and on the bits of the values: no tolerances.
+The shapes are the smallest at which the grow kernel can go wrong: rows that start at 0, 1 and on
+both sides of the 32-id gather chunk and of 64, passes that straddle a chunk boundary, rows that
+finish in different passes, a partial last 64-card tile and bit word (V = 333)."""
+import numpy as np
+import pytest
+import torch
+
+from cubecobrarecommender_amd import _lib as L
+from cubecobrarecommender_amd import api
+from cubecobrarecommender_amd.complete import plan_passes
+from cubecobrarecommender_amd.layout import Layout
+from cubecobrarecommender_amd.recommender import Recommender, pack_cubes
+from oracle import model_ref
+from tests import complete_ref
+
+pytestmark = pytest.mark.gpu
+
+SHAPES = [(333, 64), (1000, 128)]
+STEPS = [1, 4, 7]
+STARTS = [0, 1, 30, 31, 32, 33, 63, 64]
+_ctx = {}
+
+
+def rows_of(V):
+    """33 (cube, size) rows: the chunk-edge starts with growths that cross 32 / 64, rows that are
+    at or above their size, unsorted input with duplicates, and random rows; growths differ, so
+    rows finish in different passes."""
+    rng = np.random.default_rng(V)
+    grow = [9, 40, 5, 12, 3, 35, 2, 11]
+    rows = [(rng.choice(V, n, replace=False), n + g) for n, g in zip(STARTS, grow)]
+    rows.append((rng.choice(V, 20, replace=False), 20))            # at its size
+    rows.append((rng.choice(V, 40, replace=False), 7))             # above its size
+    rows.append((rng.choice(V, 5, replace=False), 0))
+    base = rng.choice(V, 25, replace=False)
+    rows.append((rng.permutation(np.concatenate([base, base[:6]])), 37))   # duplicates: 25 distinct
+    while len(rows) < 33:
+        n = int(rng.integers(0, 90))
+        rows.append((rng.choice(V, n, replace=False), n + int(rng.integers(0, 30))))
+    return rows
+
+
+def tie_columns(P, V):
+    """Output columns j and j + V // 2 made equal: those two cards tie in every pass."""
+    P = dict(P)
+    h = V // 2
+    for key in ('decoder/reconstruct/kernel', 'decoder/reconstruct/bias'):
+        a = np.array(P[key], np.float32)
+        a[..., h:2 * h] = a[..., :h]
+        P[key] = a
+    return P
+
+
+class Ctx:
+    """One shape's model and rows; the loop's results per per_step, computed once on the whole
+    batch and shared (a row's loop does not depend on its neighbours)."""
+
+    def __init__(self, V, d, ties=False):
+        self.V, self.d = V, d
+        P = model_ref.init_params(V, d, seed=V + d, bias_std=0.01)
+        self.P = tie_columns(P, V) if ties else P
+        self.rec = Recommender(Layout(V, d).pack(self.P), V, d)
+        self.rows = rows_of(V)
+        self.cubes = [c for c, _ in self.rows]
+        self.sizes = [s for _, s in self.rows]
+        self._ref = {}
+
+    def ref(self, per_step):
+        if per_step not in self._ref:
+            self._ref[per_step] = complete_ref.complete_many_loop(self.rec, self.cubes, self.sizes, per_step)
+        return self._ref[per_step]
+
+
+def ctx_of(V, d, ties=False):
+    if (V, d, ties) not in _ctx:
+        _ctx[(V, d, ties)] = Ctx(V, d, ties)
+    return _ctx[(V, d, ties)]
+
+
+def check(got, want):
+    added, vals = want[0], want[1]
+    assert got['added'].dtype == np.int32 and got['added_vals'].dtype == np.float32
+    assert np.array_equal(got['added'], added), (got['added'], added)
+    assert np.array_equal(got['added_vals'].view(np.uint32), vals.view(np.uint32))
+
+
+# ------------------------------------------------------------------------------ 1. the loop
+@pytest.mark.parametrize('per_step', STEPS)
+@pytest.mark.parametrize('V,d', SHAPES)
+def test_equals_the_loop_of_existing_calls(V, d, per_step):
+    c = ctx_of(V, d)
+    ref = c.ref(per_step)
+    grown = [len(a) for a, _, _ in ref]
+    assert len(set(grown)) > 5 and 0 in grown                      # rows finish in different passes
+    for sel in ([3], [1, 2, 3, 9, 5], list(range(33))):            # 1, 5 and 33 rows
+        got = c.rec.complete_many([c.cubes[r] for r in sel], [c.sizes[r] for r in sel], per_step=per_step)
+        assert len(got) == len(sel)
+        for g, r in zip(got, sel):
+            check(g, ref[r])
+            assert len(g['added']) == max(0, c.sizes[r] - len(np.unique(c.cubes[r])))
+    one = c.rec.complete(c.cubes[5], c.sizes[5], per_step=per_step)
+    check(one, ref[5])
+    same_size = c.rec.complete_many(c.cubes[:3], 45, per_step=per_step)   # one int for every cube
+    for r, (g, w) in enumerate(zip(same_size, complete_ref.complete_many_loop(c.rec, c.cubes[:3], 45, per_step))):
+        check(g, w)
+
+
+# ------------------------------------------------------------------------------ 2. the CPU oracle
+@pytest.mark.parametrize('per_step', [1, 3])
+def test_equals_the_cpu_oracle(per_step):
+    V, d = 96, 64
+    P = model_ref.init_params(V, d, seed=V + d, bias_std=0.01)
+    rec = Recommender(Layout(V, d).pack(P), V, d)
+    rng = np.random.default_rng(5)
+    cubes = [rng.choice(V, n, replace=False) for n in (0, 29, 50)]
+    sizes = [12, 41, 62]
+    got = rec.complete_many(cubes, sizes, per_step=per_step)
+    oracle = complete_ref.oracle_recommend(P, V)
+    for cube, size, g in zip(cubes, sizes, got):
+        want = complete_ref.complete_loop(oracle, cube, size, per_step)
+        assert len(want[0]) == 12
+        check(g, want)
+
+
+# ------------------------------------------------------------------------------ 3. insertion ends
+@pytest.mark.parametrize('per_step', [1, 7])
+def test_insertion_at_both_ends_and_interleaved(per_step):
+    c = ctx_of(333, 64)
+    cubes = [list(range(200, 260)), list(range(0, 60)), list(range(0, 120, 2))]
+    before = [list(cube) for cube in cubes]
+    got = c.rec.complete_many(cubes, 100, per_step=per_step)
+    assert cubes == before                                         # the caller's lists
+    ref = complete_ref.complete_many_loop(c.rec, cubes, 100, per_step)
+    for cube, g, w in zip(cubes, got, ref):
+        check(g, w)
+        added = g['added'].tolist()
+        assert sorted(cube + added) == w[2].tolist() and len(w[2]) == 100
+        assert len(set(added)) == len(added) and not set(added) & set(cube)
+    assert np.count_nonzero(got[0]['added'] < 200) > 5             # before every old id
+    assert np.count_nonzero(got[1]['added'] >= 60) > 5             # behind every old id
+    between = got[2]['added'][got[2]['added'] < 120]
+    assert len(between) > 0 and np.all(between % 2 == 1)           # between old ids
+
+
+# ------------------------------------------------------------------------------ 4. exhaustion
+@pytest.mark.parametrize('per_step', [1, 4])
+def test_exhaustion(per_step):
+    V, d = 70, 64
+    P = model_ref.init_params(V, d, seed=V + d, bias_std=0.01)
+    rec = Recommender(Layout(V, d).pack(P), V, d)
+    rng = np.random.default_rng(70)
+    cube = rng.choice(V, 60, replace=False)
+    missing = np.setdiff1d(np.arange(V), cube)
+    got = rec.complete(cube, 100, per_step=per_step)
+    assert sorted(got['added'].tolist()) == missing.tolist()       # exactly the 10, each once
+    check(got, complete_ref.complete_loop(complete_ref.recommender_recommend(rec), cube, 100, per_step))
+    five = rec.card_pool(np.concatenate([missing[[0, 3, 4, 7, 9]], cube[:20]]))
+    got = rec.complete(cube, 100, per_step=per_step, pool=five)
+    assert sorted(got['added'].tolist()) == missing[[0, 3, 4, 7, 9]].tolist()
+    check(got, complete_ref.complete_loop(complete_ref.recommender_recommend(rec), cube, 100, per_step, pool=five))
+    inside = rec.card_pool(cube[:30])
+    got = rec.complete(cube, 100, per_step=per_step, pool=inside)
+    assert len(got['added']) == 0 and len(got['added_vals']) == 0
+    assert len(rec.complete(np.arange(V), 100, per_step=per_step)['added']) == 0   # n == V
+
+
+# ------------------------------------------------------------------------------ 5. pools
+@pytest.mark.parametrize('per_step', [1, 4])
+def test_pools(per_step):
+    V, d = 333, 64
+    c = ctx_of(V, d)
+    rng = np.random.default_rng(9)
+    even = c.rec.card_pool(np.arange(0, V, 2))
+    few = c.rec.card_pool(rng.choice(V, 40, replace=False))
+    sel = list(range(12))
+    cubes, sizes = [c.cubes[r] for r in sel], [c.sizes[r] for r in sel]
+    pools = [(even, None, few)[r % 3] for r in sel]
+    got = c.rec.complete_many(cubes, sizes, per_step=per_step, pool=pools)
+    ref = complete_ref.complete_many_loop(c.rec, cubes, sizes, per_step, pools=pools)
+    for r, (g, w) in enumerate(zip(got, ref)):
+        check(g, w)
+        if pools[r] is not None:
+            assert np.all(pools[r].contains(g['added']))
+        else:
+            check(g, c.ref(per_step)[r])
+    assert any(len(g['added']) > 3 for g, p in zip(got, pools) if p is few)
+    one_pool = c.rec.complete_many(cubes, sizes, per_step=per_step, pool=even)
+    for g, w in zip(one_pool, complete_ref.complete_many_loop(c.rec, cubes, sizes, per_step, pools=[even] * 12)):
+        check(g, w)
+
+
+# ------------------------------------------------------------------------------ 6. batch independence
+def test_batch_independence():
+    c = ctx_of(333, 64)
+    per_step = 4
+    ref = c.ref(per_step)
+    whole = c.rec.complete_many(c.cubes, c.sizes, per_step=per_step, rows_per_launch=512)
+    pairs = c.rec.complete_many(c.cubes, c.sizes, per_step=per_step, rows_per_launch=2)
+    for r in range(33):
+        check(whole[r], ref[r])
+        check(pairs[r], ref[r])
+    for r in (0, 1, 7, 11, 32):
+        check(c.rec.complete_many([c.cubes[r]], [c.sizes[r]], per_step=per_step)[0], ref[r])
+    twins = c.rec.complete_many([c.cubes[1], c.cubes[5], c.cubes[1].copy()], [c.sizes[1], c.sizes[5], c.sizes[1]],
+                                per_step=per_step)
+    check(twins[0], ref[1])
+    check(twins[2], ref[1])
+
+
+# ------------------------------------------------------------------------------ 7. ties
+@pytest.mark.parametrize('per_step', [1, 4])
+def test_ties(per_step):
+    V, d = 333, 64
+    c = ctx_of(V, d, ties=True)
+    ref = c.ref(per_step)
+    got = c.rec.complete_many(c.cubes, c.sizes, per_step=per_step)
+    tied = 0
+    for g, w in zip(got, ref):
+        check(g, w)
+        a, v = g['added'], g['added_vals']
+        for i in range(0, len(a) - 1):
+            if (i + 1) % per_step and v[i] == v[i + 1]:             # both of one pass
+                assert a[i] > a[i + 1]                              # equal values: higher card index first
+                tied += 1
+    if per_step > 1:
+        assert tied > 0
+
+
+# ------------------------------------------------------------------------------ 8. the C entry
+def _direct(rec, cubes, sizes, per_step, extra_passes=0, pool_words=None, pool_of_row=None, ws_shift=0,
+            passes=None, over=None):
+    V, d, dev = rec.V, rec.d, rec.dev
+    row_ptr, idx, _, _, _ = pack_cubes(cubes, V)
+    R = len(cubes)
+    target, need, A, max_n = plan_passes(np.diff(row_ptr), sizes, per_step, V)
+    A += 3                                                          # a pitch above the need: a tail in every row
+    rp = torch.from_numpy(row_ptr).to(dev)
+    ix = torch.from_numpy(idx if len(idx) else np.zeros(1, np.int32)).to(dev)
+    tn = torch.from_numpy(target).to(dev)
+    ws = torch.full((int(L.lib().cc_complete_ws_size(V, d, R, max_n, per_step)) // 4 + 64,), -1, device=dev,
+                    dtype=torch.int32)
+    assert ws.data_ptr() % 256 == 0
+    nadd = torch.full((R,), 77, device=dev, dtype=torch.int32)
+    adds = torch.full((R, A), 77, device=dev, dtype=torch.int32)
+    addv = torch.full((R, A), 7.0, device=dev)
+    table = por = None
+    if pool_words is not None:
+        table = torch.from_numpy(np.stack(pool_words).view(np.int32)).to(dev)
+        por = torch.tensor(pool_of_row, device=dev, dtype=torch.int32)
+    args = dict(params=L.ptr(rec.params), V=V, d=d, R=R, row_ptr=L.ptr(rp), idx=L.ptr(ix), max_n=max_n,
+                target_n=L.ptr(tn), per_step=per_step, passes=need + extra_passes if passes is None else passes,
+                pools=L.ptr(table), n_pools=0 if pool_words is None else len(pool_words), pool_of_row=L.ptr(por),
+                A=A, n_added=L.ptr(nadd), added=L.ptr(adds), added_vals=L.ptr(addv),
+                ws=L.C.c_void_p(ws.data_ptr() + ws_shift), ws_bytes=ws.numel() * 4 - ws_shift,
+                stream=L.stream_ptr())
+    args.update(over or {})
+    rc = L.lib().cc_complete_fp32(*args.values())
+    torch.cuda.synchronize()
+    return dict(rc=rc, nadd=nadd.cpu().numpy(), adds=adds.cpu().numpy(), addv=addv.cpu().numpy(),
+                row_ptr=rp.cpu().numpy(), idx=ix.cpu().numpy(), need=need)
+
+
+@pytest.mark.parametrize('per_step', [1, 7])
+def test_direct_call(per_step):
+    c = ctx_of(333, 64)
+    ref = c.ref(per_step)
+    sel = list(range(14))
+    cubes, sizes = [c.cubes[r] for r in sel], [c.sizes[r] for r in sel]
+    row_ptr, idx, _, _, _ = pack_cubes(cubes, c.V)
+    exact = _direct(c.rec, cubes, sizes, per_step)
+    more = _direct(c.rec, cubes, sizes, per_step, extra_passes=5)   # finished rows are carried along
+    assert exact['need'] == -(-40 // per_step)
+    for out in (exact, more):
+        assert out['rc'] == 0
+        assert np.array_equal(out['row_ptr'], row_ptr) and np.array_equal(out['idx'], idx)   # inputs not written
+        for i, r in enumerate(sel):
+            k = out['nadd'][i]
+            assert k == len(ref[r][0])
+            assert np.array_equal(out['adds'][i, :k], ref[r][0])
+            assert np.array_equal(out['addv'][i, :k].view(np.uint32), ref[r][1].view(np.uint32))
+            assert np.all(out['adds'][i, k:] == -1) and np.all(out['addv'][i, k:] == 0.0)
+            assert out['adds'].shape[1] > k                        # there was a tail to check
+    # fewer passes than needed: a prefix of every row's picks, whole passes of it
+    short = _direct(c.rec, cubes, sizes, per_step, passes=2)
+    for i, r in enumerate(sel):
+        k = min(len(ref[r][0]), 2 * per_step)
+        assert short['nadd'][i] == k and np.array_equal(short['adds'][i, :k], ref[r][0][:k])
+        assert np.all(short['adds'][i, k:] == -1)
+    # pools through the entry: pool 0, none, a value that is no pool of the table (no candidates)
+    even = np.zeros((c.V + 31) // 32, np.uint32)
+    ids = np.arange(0, c.V, 2)
+    np.bitwise_or.at(even, ids >> 5, np.uint32(1) << (ids & 31).astype(np.uint32))
+    por = [(0, -1, 1)[i % 3] for i in range(len(sel))]
+    pooled = _direct(c.rec, cubes, sizes, per_step, pool_words=[even], pool_of_row=por)
+    assert pooled['rc'] == 0
+    pool = c.rec.card_pool(ids)
+    want = complete_ref.complete_many_loop(c.rec, cubes, sizes, per_step, pools=[(pool, None, None)[i % 3] for i in range(len(sel))])
+    for i in range(len(sel)):
+        k = pooled['nadd'][i]
+        if por[i] == 1:
+            assert k == 0 and np.all(pooled['adds'][i] == -1)
+            continue
+        assert k == len(want[i][0]) and np.array_equal(pooled['adds'][i, :k], want[i][0])
+        assert np.array_equal(pooled['addv'][i, :k].view(np.uint32), want[i][1].view(np.uint32))
+    # nothing launched: the outputs keep their junk
+    lib = L.lib()
+    for kw, word in ((dict(ws_shift=4), b'aligned'), (dict(over=dict(per_step=0)), b'per_step'),
+                     (dict(over=dict(per_step=lib.cc_complete_max_per_step() + 1)), b'per_step'),
+                     (dict(passes=-1), b'passes'), (dict(over=dict(ws_bytes=1024)), b'workspace')):
+        out = _direct(c.rec, cubes, sizes, per_step, **kw)
+        assert out['rc'] == -1 and word in lib.cc_last_error_string(), word
+        assert np.all(out['nadd'] == 77) and np.all(out['adds'] == 77) and np.all(out['addv'] == 7.0)
+    out = _direct(c.rec, cubes, sizes, per_step, passes=0)
+    assert out['rc'] == 0 and np.all(out['nadd'] == 77) and np.all(out['adds'] == 77)
+
+
+# ------------------------------------------------------------------------------ 9. api
+def test_api_json_shape():
+    V, d = 63, 64
+    P = model_ref.init_params(V, d, seed=V + d, bias_std=0.01)
+    rec = Recommender(Layout(V, d).pack(P), V, d)
+
+    class Model:
+        def recommender(self):
+            return rec
+    names = {i: f'card {i}' for i in range(V)}
+    cube = [5, 9, 5, 40, 2]
+    for per_step, pool in ((1, None), (3, rec.card_pool(np.arange(1, V, 2)))):
+        got = api.complete_cube(Model(), iter(cube), 12, names, pool=pool, per_step=per_step)
+        want = complete_ref.complete_loop(complete_ref.recommender_recommend(rec), cube, 12, per_step, pool=pool)
+        assert list(got) == ['additions'] and len(got['additions']) == 8
+        assert list(got['additions']) == [names[i] for i in want[0].tolist()]          # in pick order
+        assert list(got['additions'].values()) == want[1].tolist()
+        assert all(type(v) is float for v in got['additions'].values())
+    assert api.complete_cube(Model(), cube, 3, names) == {'additions': {}}
