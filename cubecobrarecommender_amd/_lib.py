@@ -180,6 +180,13 @@ SIGNATURES = {
     'cc_cube_neighbours_max_k': (_I32, []),
     'cc_cube_neighbours_ws_size': (_SZ, [_I32, _I32, _I32, _I32, _I32]),
     'cc_cube_neighbours': (C.c_int, [_P, _I32, _I32, _I32, _I32, _P, _P, _P, _I32, _I32, _P, _P, _P, _P]),
+    'cc_audience_corpus_size': (_SZ, [_I32, _I32, _I32]),
+    'cc_audience_put_ws_size': (_SZ, [_I32, _I32, _I32]),
+    'cc_audience_put': (C.c_int, [_P, _I32, _I32, _P, _I32, _I32, _I32, _I32, _I32, _P, _P, _I32, _I32, _P, _P]),
+    'cc_audience_max_k': (_I32, []),
+    'cc_audience_ws_size': (_SZ, [_I32, _I32, _I32, _I32, _I32]),
+    'cc_audience_fp32': (C.c_int, [_P, _I32, _I32, _P, _I32, _I32, _I32, _P, _I32, _I32, _I32, _F32, _P, _P, _P, _P,
+                                   _P]),
     'cc_embed_grad_packed': (C.c_int, [_P, _I32, _I32, _I32, _I32, _P, _P, _P, _P]),
     **{w1_grad_name(*form): (C.c_int, _w1_grad_args(*form)) for form in W1_GRAD_FORMS},
     'cc_embed_grad_cs_tickets': (_I32, [_I32, _I32, _I32]),

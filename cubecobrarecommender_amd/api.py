@@ -98,6 +98,26 @@ def similar_cubes(index, cube_indices, k, cube_names=None):
             for i, (j, dv) in enumerate(zip(idx[0], dists[0]))]
 
 
+def card_audience(corpus, card_names, k, card_to_int, cube_names=None, include_members=False):
+    """"Which cubes want this card" against an audience.CubeCorpus (model.cube_corpus(cubes)): per
+    card name of card_names a list of (cube, prob), the up to k cubes with the highest
+    p(card | cube) among those that do not play the card yet (every cube with include_members),
+    best first, equal probabilities lower cube id first.  cube is the corpus's cube id, or
+    cube_names[id] with cube_names (a sequence or a dict).  Names are normalised as
+    cube_indices_of does; one the model does not know raises KeyError naming it."""
+    card_names = list(card_names)
+    ids = []
+    for name in card_names:
+        idx = card_to_int.get(normalize(name))
+        if idx is None:
+            raise KeyError(f'unknown card {name!r}')
+        ids.append(idx)
+    out = corpus.audience(ids, k, include_members=include_members)
+    return [[(int(j) if cube_names is None else cube_names[int(j)], float(p))
+             for j, p in zip(row[:found].tolist(), prow[:found].tolist())]
+            for row, prow, found in zip(out['cubes'], out['probs'], out['found'].tolist())]
+
+
 def leave_one_out_cuts(model, cube_indices, int_to_card):
     """Honest cut values of one cube: {name: (with, without)} with `with` = p(c | cube), the value
     `recommend` reports under "cuts", and `without` = p(c | cube without c)

@@ -35,6 +35,7 @@
 
 #include "common.hpp"
 #include "detmath.hpp"
+#include "rowselect.hpp"
 #include "rowsort.hpp"
 
 namespace {
@@ -44,16 +45,18 @@ constexpr int TC = 64;        // cubes per distance tile
 constexpr int DNT = 256;      // distance-tile workgroup: 16 cube groups x 16 query groups
 constexpr int NR = 128;       // put: rows per workgroup, one thread each
 constexpr int QNT = 64;       // query rows: one thread each
-constexpr int SNT = 1024;     // select workgroup
-constexpr int MAX_K = 1024;   // neighbours per query
-constexpr int MAX_SEL = 2048; // survivors sorted in LDS
 constexpr int MAX_Q = 1 << 22;
 constexpr int DEFAULT_CHUNK = 1 << 16;
-constexpr uint64_t NONE = ~0ull;  // no candidate: above every composite of a finite distance
 
 using detm::addf;
 using detm::mulf;
 using rowsort::orderable;
+using rowsel::CandItem;
+using rowsel::MAX_K;  // neighbours per query
+using rowsel::NONE;   // above every composite of a finite distance
+using rowsel::select_smallest;
+using rowsel::SelectLds;
+using rowsel::SNT;
 
 // orderable's inverse on distances: the only zero a distance takes is -0.0f (simbatch.hip)
 __device__ __forceinline__ float dist_of_key(uint32_t key) {
@@ -235,78 +238,6 @@ __global__ __launch_bounds__(DNT, 4) void dist_chunk_kernel(const float *__restr
   }
 }
 
-// The LDS of one select (select_rows_kernel's).
-struct SelectLds {
-  uint32_t hist[1024];
-  int wtot[SNT / 64];
-  uint64_t prefix, mask;
-  int rem, done, cnt;
-  uint64_t sel[MAX_SEL];
-};
-
-// The `want` smallest of the composites item(0..count) that are not NONE, ascending in s.sel[0..want);
-// 1 <= want <= MAX_K and at most the number of such items.  id_max: no composite has a bit of its low
-// word above id_max's.  select_rows_kernel's radix select (10-bit digits from the top, windows split
-// at bit 32, stopping once the composites at or below the chosen bin fit the sort) and bitonic sort.
-template <class Item>
-__device__ __forceinline__ void select_smallest(SelectLds &s, const Item &item, int count, int want,
-                                                uint32_t id_max) {
-  const int tid = threadIdx.x;
-  int PN = 1;
-  while (PN < want) PN <<= 1;
-  const int limit = min(MAX_SEL, 2 * PN);
-  if (tid == 0) {
-    s.prefix = 0;
-    s.mask = 0;
-    s.rem = want;
-    s.done = 0;
-    s.cnt = 0;
-  }
-  __syncthreads();
-  for (int pass = 0; pass < 8; ++pass) {
-    const int shift = pass < 3 ? 54 - 10 * pass : pass == 3 ? 32 : pass < 7 ? 22 - 10 * (pass - 4) : 0;
-    const uint32_t dmask = (pass == 3 || pass == 7) ? 3u : 1023u;
-    if (shift < 32 && (id_max >> shift) == 0u) continue;  // no id has a bit up here
-    if (s.done) break;
-    const uint64_t prefix = s.prefix, mask = s.mask;
-    const int rem = s.rem;
-    s.hist[tid] = 0u;
-    __syncthreads();
-    for (int j = tid; j < count; j += SNT) {
-      const uint64_t cmp = item(j);
-      if (cmp != NONE && (cmp & mask) == prefix) atomicAdd(&s.hist[(uint32_t)(cmp >> shift) & dmask], 1u);
-    }
-    __syncthreads();
-    // thread t owns bin t: its inclusive scan is the count of matching items in bins <= it
-    const int v = (int)s.hist[tid];
-    const int le = rowsort::block_incl_scan<SNT>(v, s.wtot), lt = le - v;
-    if (le >= rem && lt < rem) {  // exactly one bin: the one holding the rem-th smallest
-      s.prefix = prefix | ((uint64_t)tid << shift);
-      s.mask = mask | ((uint64_t)dmask << shift);
-      s.rem = rem - lt;
-      s.done = (want - (rem - lt)) + v <= limit;  // everything at or below this bin: want or a few more
-    }
-    __syncthreads();
-  }
-  // the bits outside the mask are below every decided digit or zero in every composite: on the
-  // decided bits, a candidate <=> at or below the prefix; all passes done, exactly `want` of them
-  const uint64_t T = s.prefix, M = s.mask;
-  for (int j = tid; j < count; j += SNT) {
-    const uint64_t cmp = item(j);
-    if (cmp != NONE && (cmp & M) <= T) {
-      const int pos = atomicAdd(&s.cnt, 1);
-      if (pos < limit) s.sel[pos] = cmp;
-    }
-  }
-  __syncthreads();
-  const int cnt = min(s.cnt, limit);  // (want <= cnt <= limit by the counts; never past sel)
-  int P = PN;
-  while (P < cnt) P <<= 1;
-  for (int i = cnt + tid; i < P; i += SNT) s.sel[i] = NONE;
-  __syncthreads();
-  rowsort::bitonic_sort<SNT>(P, rowsort::CmpSwapU64<false>{s.sel});
-}
-
 struct ChunkItem {  // key << 32 | cube position inside the chunk; the skipped cube is no candidate
   const uint32_t *k;
   int skip;
@@ -315,11 +246,6 @@ struct ChunkItem {  // key << 32 | cube position inside the chunk; the skipped c
     return j == skip ? NONE : cmp;
   }
 };
-struct CandItem {
-  const uint64_t *c;
-  __device__ __forceinline__ uint64_t operator()(int j) const { return c[j]; }
-};
-
 // The first `want` entries of s.sel as a result row, then the -1 / 0.f tail.
 __device__ __forceinline__ void write_row(const SelectLds &s, int want, int k, int32_t *oi, float *od) {
   for (int i = threadIdx.x; i < want; i += SNT) {

@@ -285,6 +285,12 @@ class CC_Recommender:
         from .cubesim import CubeIndex
         return CubeIndex(self.recommender(), cubes, capacity=capacity)
 
+    def cube_corpus(self, cubes, capacity=None, card_capacity=None):
+        """A resident corpus of `cubes` (card-index lists) under the current weights' forward pass,
+        for "which cubes want this card": audience.CubeCorpus (audience, add)."""
+        from .audience import CubeCorpus
+        return CubeCorpus(self.recommender(), cubes, capacity=capacity, card_capacity=card_capacity)
+
     def evaluate_holdout(self, cubes, **kw):
         """Held-out ranking metrics (recall@K, NDCG@K, hit rate@K, MRR) of the current weights on
         `cubes` (card-index lists): evaluate.evaluate_holdout through the resident recommender."""

@@ -269,6 +269,12 @@ class Recommender:
         from .cubesim import CubeIndex
         return CubeIndex(self, cubes, capacity=capacity)
 
+    def cube_corpus(self, cubes, capacity=None, card_capacity=None):
+        """A resident corpus of `cubes` (card-index lists) under this model's forward pass, for
+        "which cubes want this card" (audience.CubeCorpus)."""
+        from .audience import CubeCorpus
+        return CubeCorpus(self, cubes, capacity=capacity, card_capacity=card_capacity)
+
     # ------------------------------------------------------------------ card pools
     def card_pool(self, ids):
         """A CardPool of `ids` for this model with its bit row on the device: uploaded once, then

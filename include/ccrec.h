@@ -725,6 +725,49 @@ int cc_cube_neighbours(const void *index, int32_t cap, int32_t N, int32_t K, int
                        int32_t chunk, void *ws, int32_t *out_idx, float *out_dist, void *stream);
 
 /* ----------------------------------------------------------------------------------
+ * Card audience: a resident corpus of N cubes (ids are positions) and, for T query cards, the k
+ * cubes that want each card most.  p[t][c] = det_sigmoid32(blocked_dot(h3[c], Wo[:, t]) + bo[t])
+ * with h3[c] the forward pass of cube c: the bits of cc_recommend_batch_fp32's probs[c][t] and of
+ * cc_leave_one_out_fp32's base row.  Per card the candidates are the corpus cubes that do not
+ * hold it (every cube with include_members != 0), ranked by descending p, equal p lower cube id
+ * first: a total order, so no output bit depends on chunk, on the batch a card falls into or on
+ * the pieces in which the corpus was put.
+ * The corpus is opaque, caller-owned, 256-byte aligned, cc_audience_corpus_size(cap, card_cap, d)
+ * bytes: h3 [cap][d] fp32, ptr [cap + 1] and ids [card_cap], the cubes' sorted distinct card ids.
+ *   cc_audience_put: the forward pass of R cubes given as CSR (row_ptr [R + 1] with row_ptr[0] == 0
+ *     and row_ptr[R] == nnz, idx [nnz]: sorted distinct ids in [0, V) per row, the PRECONDITIONS of
+ *     cc_recommend_batch_fp32; max_n >= the longest row; all on the device) into corpus rows
+ *     [n0, n0 + R), their ids into [nnz0, nnz0 + nnz) and ptr [n0, n0 + R].  Cubes are appended:
+ *     the put of rows [n0, ..) starts its ids where the rows before it end.  A row's bits do not
+ *     depend on where a put starts or ends.  nnz is passed because the entry cannot read row_ptr;
+ *     R <= 65535.  ws: cc_audience_put_ws_size(R, d, max_n) bytes, 256-byte aligned.  R == 0 returns
+ *     CC_OK and launches nothing.
+ *     CC_ERR_ARG, nothing launched: null or unaligned pointer, n0 + R > cap, nnz0 + nnz > card_cap,
+ *     nnz > R * max_n, max_n > V, d not a multiple of 64 in [64, 1024].
+ *   cc_audience_fp32: cards [T] (device); a card outside [0, V) is never used as an index: its row
+ *     is -1 / 0.f with zero counts.  Duplicate cards are independent rows.  out_idx / out_p [T][k]:
+ *     the first min(k, candidates) entries in rank order, then -1 / 0.f.  out_counts [T][3]:
+ *     members (corpus cubes holding the card), candidates, and candidates with p >= threshold
+ *     (fp32 compare).  1 <= k <= cc_audience_max_k() (at least 1024), T <= 4096, threshold in
+ *     [0, 1].  chunk: corpus cubes per pass, 0 for the default, else a positive multiple of 64 up
+ *     to 2^20.  Only rows [0, N) of the corpus are read.  ws: cc_audience_ws_size(N, d, T, k, chunk)
+ *     bytes, 256-byte aligned: the gathered columns d * T, T * min(chunk, N) sort keys and
+ *     T * k * ceil(N / chunk) candidates, never T * N; nothing in it is assumed to survive from an
+ *     earlier call.  T == 0 returns CC_OK and launches nothing.
+ * ---------------------------------------------------------------------------------- */
+size_t cc_audience_corpus_size(int32_t cap, int32_t card_cap, int32_t d);
+size_t cc_audience_put_ws_size(int32_t R, int32_t d, int32_t max_n);
+int cc_audience_put(const float *params, int32_t V, int32_t d, void *corpus, int32_t cap,
+                    int32_t card_cap, int32_t n0, int32_t nnz0, int32_t R, const int32_t *row_ptr,
+                    const int32_t *idx, int32_t nnz, int32_t max_n, void *ws, void *stream);
+int32_t cc_audience_max_k(void);
+size_t cc_audience_ws_size(int32_t N, int32_t d, int32_t T, int32_t k, int32_t chunk);
+int cc_audience_fp32(const float *params, int32_t V, int32_t d, const void *corpus, int32_t cap,
+                     int32_t N, int32_t T, const int32_t *cards, int32_t k, int32_t chunk,
+                     int32_t include_members, float threshold, void *ws, int32_t *out_idx,
+                     float *out_p, int32_t *out_counts, void *stream);
+
+/* ----------------------------------------------------------------------------------
  * Top-N (ml_recommend.py:87-108): rank all V probabilities descending, ties -> higher
  * index first (= numpy argsort(kind='stable')[::-1]); additions = first max(amount,1)
  * indices not in the cube; cut_vals[i] = probs[cube_idx[i]].  cube_idx: n DISTINCT card ids.
