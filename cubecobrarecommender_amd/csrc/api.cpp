@@ -4,6 +4,7 @@
 #include <string>
 
 #include "common.hpp"
+#include "infer.hpp"
 
 namespace cc {
 static thread_local std::string g_last_error;

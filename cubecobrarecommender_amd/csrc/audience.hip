@@ -17,8 +17,8 @@
 //                        columns for the pad and for cards outside [0, V)), their biases, the
 //                        checked cards, and zeroes the counts.  The only V-strided loads.
 // then per chunk of the corpus (cubes [c0, c0 + cl)), so that the keys are [T][chunk], never [T][N],
-//   score_chunk_kernel : 64 cubes x 64 cards per workgroup, loo_tile_kernel's arithmetic (stages
-//                        of 32 k, acc into tot at every 64-k boundary).  The card tiles of one
+//   score_chunk_kernel : 64 cubes x 64 cards per workgroup, the dot-product tile of DESIGN.md
+//                        4.10 in the pinned chunks (out_tile_kernel's loop, restated).  The card tiles of one
 //                        cube tile are neighbouring workgroups: h3 comes from HBM once per chunk.
 //                        Membership: the tile's 64 cards sorted in LDS (equal runs kept); the
 //                        tile's cubes are one segment of ids, read coalesced by all threads with
@@ -38,32 +38,22 @@
 
 #include "common.hpp"
 #include "detmath.hpp"
+#include "dottile.hpp"
+#include "infer.hpp"
 #include "rowselect.hpp"
 #include "rowsort.hpp"
 
-namespace cc {
-int param_offsets(int V, int d, int64_t *off, int64_t *size, int64_t *total, int64_t *main_total);
-// infer.hip
-int infer_check_d(int d, const char *who);
-int infer_gather_cap(int max_n);
-int infer_h3_launch(const float *params, int V, int d, int R, const int32_t *row_ptr,
-                    const int32_t *idx, int max_n, float *part, float *zlat, float *h3,
-                    hipStream_t s);
-}  // namespace cc
-
 namespace {
 
-constexpr int KCH = 64;   // dot chunk (pinned)
-constexpr int KS = 32;    // k per LDS stage of the score tile
-constexpr int TC = 64;    // cards per score tile
-constexpr int RM = 4;     // cubes per thread of the score tile
+constexpr int KCH = dottile::KCH, KS = dottile::KS;  // the tile's constants (dottile.hpp)
+constexpr int TC = dottile::TC;   // cards per score tile
+constexpr int RM = 4;             // cubes per thread of the score tile
 constexpr int TR = 16 * RM;
-constexpr int ONT = 256;  // score-tile workgroup: 16 card groups x 16 cube groups
+constexpr int ONT = dottile::NT;  // score-tile workgroup
 constexpr int GNT = 256;  // gather / put workgroup
 constexpr int BLOOM = 2048;  // bits of a tile's card filter, by the id's low bits
 constexpr int MAX_T = 4096;
 constexpr int MAX_PUT_ROWS = 65535;  // the gather's grid.y
-constexpr int DEFAULT_CHUNK = 1 << 16;
 constexpr int MAX_CHUNK = 1 << 20;
 constexpr uint32_t MEMBER = 0xFFFFFFFFu;  // no candidate: real keys end at orderable(-0.f) = 0x80000000
 
@@ -75,12 +65,9 @@ using rowsel::NONE;
 using rowsel::select_smallest;
 using rowsel::SelectLds;
 using rowsel::SNT;
+using rowsel::write_row;
 using rowsort::orderable;
 
-// an id outside [0, V) is never used as an index: it travels as -1
-__device__ __forceinline__ int32_t card_or_none(int32_t id, int V) {
-  return (uint32_t)id < (uint32_t)V ? id : -1;
-}
 // orderable's inverse on keys of -p, p >= 0: the zero comes back as +0.f
 __device__ __forceinline__ float prob_of_key(uint32_t key) {
   return (key & 0x80000000u) ? 0.f : __uint_as_float(~key & 0x7FFFFFFFu);
@@ -197,7 +184,7 @@ __global__ __launch_bounds__(ONT, 4) void score_chunk_kernel(
     }
   }
 
-  // ---- scores
+  // ---- scores: out_tile_kernel's loop (recbatch.hip), statement for statement
   float tot[RM][4], acc[RM][4];
 #pragma unroll
   for (int j = 0; j < RM; ++j)
@@ -316,19 +303,6 @@ struct KeyItem {  // key << 32 | cube position inside the chunk; a member is no 
   }
 };
 
-// The first `want` entries of s.sel as a result row, then the -1 / 0.f tail.
-__device__ __forceinline__ void write_row(const SelectLds &s, int want, int k, int32_t *oi, float *op) {
-  for (int i = threadIdx.x; i < want; i += SNT) {
-    const uint64_t cmp = s.sel[i];
-    oi[i] = (int32_t)(uint32_t)cmp;
-    op[i] = prob_of_key((uint32_t)(cmp >> 32));
-  }
-  for (int i = max(want, 0) + threadIdx.x; i < k; i += SNT) {
-    oi[i] = -1;
-    op[i] = 0.f;
-  }
-}
-
 // Candidates of (card t, this chunk): cand[t][chunk][0..k), global cube ids, NONE behind the last.
 // cnt[t] is the chunk's candidate count, taken and cleared for the next chunk's score launch.
 // FINAL (the corpus is one chunk): the chunk's candidates are the row's result, written as such.
@@ -350,7 +324,7 @@ __global__ __launch_bounds__(SNT) void select_chunk_kernel(const uint32_t *__res
   const int want = min(k, min(max(s_n, 0), cl));  // (block-uniform)
   if (want > 0) select_smallest(s, KeyItem{keys + (int64_t)t * pitch}, cl, want, (uint32_t)(cl - 1));
   if (FINAL) {
-    write_row(s, want, k, out_idx + (int64_t)t * k, out_p + (int64_t)t * k);  // c0 == 0
+    write_row(s, want, k, out_idx + (int64_t)t * k, out_p + (int64_t)t * k, prob_of_key);  // c0 == 0
   } else {
     uint64_t *out = cand + ((int64_t)t * chunks + chunk_no) * k;
     // c0 + position < 2^31: the sum stays inside the low word
@@ -368,7 +342,7 @@ __global__ __launch_bounds__(SNT) void merge_rows_kernel(const uint64_t *__restr
   const int want = min(k, min(max(out_counts[3 * t + 1], 0), N));  // (block-uniform)
   // chunks * k stays below 2^31: larger counts are refused by the entry
   if (want > 0) select_smallest(s, CandItem{cand + (int64_t)t * chunks * k}, chunks * k, want, (uint32_t)(N - 1));
-  write_row(s, want, k, out_idx + (int64_t)t * k, out_p + (int64_t)t * k);
+  write_row(s, want, k, out_idx + (int64_t)t * k, out_p + (int64_t)t * k, prob_of_key);
 }
 
 // corpus: [h3 cap*d][ptr cap+1][ids card_cap]; the offsets do not depend on card_cap
@@ -402,17 +376,14 @@ PutWs put_ws(int R, int d, int max_n) {
 // query workspace: [wT d*Tp][bo Tp][card Tp][cnt Tp][keys T*pitch][cand T*chunks*k], pitch = the
 // chunk, or N rounded up to 64 where that is less: it grows with T * chunk and T * k * chunks,
 // never with T * N
-struct QueryWs {
+struct QueryWs : rowsel::ChunkPlan {
   size_t wT, bo, card, cnt, keys, cand, total;
-  int Tp, chunk, pitch, chunks;
+  int Tp;
 };
 QueryWs query_ws(int N, int d, int T, int k, int chunk) {
-  QueryWs w;
-  const size_t t = (size_t)std::max(T, 1), n = (size_t)std::max(N, 1), dd = (size_t)std::max(d, 64);
+  QueryWs w{rowsel::chunk_plan(N, chunk)};
+  const size_t t = (size_t)std::max(T, 1), dd = (size_t)std::max(d, 64);
   w.Tp = (int)cdiv((int64_t)t, TC) * TC;
-  w.chunk = chunk > 0 ? chunk : DEFAULT_CHUNK;
-  w.pitch = (int)std::min<size_t>((size_t)w.chunk, (size_t)cdiv((int64_t)n, 64) * 64);
-  w.chunks = (int)cdiv((int64_t)n, w.chunk);
   size_t o = 0;
   w.wT = o, o += align256(dd * w.Tp * sizeof(float));
   w.bo = o, o += align256((size_t)w.Tp * sizeof(float));

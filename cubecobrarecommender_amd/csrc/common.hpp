@@ -76,6 +76,11 @@ template <> struct DT<bf16_t> {
   static constexpr int code = CC_BF16;
 };
 
+// an id outside [0, V) is never used as an index: it travels as -1
+__device__ __forceinline__ int32_t card_or_none(int32_t id, int V) {
+  return (uint32_t)id < (uint32_t)V ? id : -1;
+}
+
 __host__ __device__ static inline int64_t cdiv(int64_t a, int64_t b) { return (a + b - 1) / b; }
 // workspace sections start on 256-byte boundaries
 __host__ __device__ static inline size_t align256(size_t x) { return (x + 255) & ~(size_t)255; }

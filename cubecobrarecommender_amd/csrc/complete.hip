@@ -13,19 +13,7 @@
 // t reads one (pass 0 the caller's) and grow_kernel writes the other.  All grids come from host
 // sizes; nothing is read back between passes and no workgroup waits for another.
 #include "common.hpp"
-
-namespace cc {
-// infer.hip
-int infer_check_d(int d, const char *who);
-// recbatch.hip
-int batch_max_amount();
-size_t batch_select_ws_bytes(int V, int d, int R, int max_n, bool pooled);
-int batch_select_launch(const float *params, int V, int d, int R, const int32_t *row_ptr,
-                        const int32_t *idx, int max_n, int amount, void *ws, int32_t *n_add,
-                        int32_t *additions, float *add_vals, float *cut_vals, float *probs,
-                        const uint32_t *pools, int n_pools, const int32_t *pool_of_row,
-                        hipStream_t s);
-}  // namespace cc
+#include "infer.hpp"
 
 namespace {
 

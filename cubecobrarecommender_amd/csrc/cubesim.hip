@@ -8,17 +8,18 @@
 // The index is n [cap][Kp] (row-major, for member queries) and nT [Kp][caps] (k-major, for the
 // corpus side of the distance tile), Kp = K rounded up to the tile's k stage, caps = cap rounded
 // up to 64.  It is written by puts alone and normalised once:
-//   put_rows_kernel   : simbatch.hip's normalise_kernel at a row offset.  One thread per row, so a
-//                       row's bits do not depend on where a put starts or ends; the k pad of the
-//                       rows it writes is written as zeros.
+//   normalise_kernel  : simbatch.hip's, at the put's row offset (cc::normalise_rows_launch).  One
+//                       thread per row, so a row's bits do not depend on where a put starts or
+//                       ends; the k pad of the rows it writes is written as zeros.
 // A search runs, once per call,
 //   query_rows_kernel : one 64-thread workgroup per query.  A member's row is copied from n, a
 //                       fresh embedding is normalised by put's arithmetic (staged through LDS, the
 //                       sum by one thread in index order), into qn [Q][Kp]; qok [Q] says whether the
 //                       row is a query at all (an id outside [0, N) never is).
 // then per chunk of the corpus (cubes [c0, c0 + cl)), so that the keys are [Q][chunk], never [Q][N],
-//   dist_chunk_kernel : simbatch.hip's distance tile, 16*RM queries x 64 cubes per workgroup, the
-//                       query rows from qn, the cubes from nT at c0.  Writes orderable(-dot).
+//   dist_chunk_kernel : simbatch.hip's distance tile (dottile.hpp), 16*RM queries
+//                       x 64 cubes per workgroup, the query rows from qn, the cubes from nT at c0.
+//                       Writes orderable(-dot).
 //   select_chunk_kernel: one workgroup per query.  The chunk's min(k, population) smallest
 //                       composites, the row's skip left out, by the radix select and bitonic sort
 //                       of select_rows_kernel, stored with global cube ids as candidates
@@ -34,19 +35,18 @@
 #include <algorithm>
 
 #include "common.hpp"
+#include "cosine.hpp"
 #include "detmath.hpp"
+#include "dottile.hpp"
 #include "rowselect.hpp"
 #include "rowsort.hpp"
 
 namespace {
 
-constexpr int KS = 32;        // k per LDS stage of the distance tile
-constexpr int TC = 64;        // cubes per distance tile
-constexpr int DNT = 256;      // distance-tile workgroup: 16 cube groups x 16 query groups
-constexpr int NR = 128;       // put: rows per workgroup, one thread each
+constexpr int TC = dottile::TC;   // cubes per distance tile
+constexpr int DNT = dottile::NT;  // distance-tile workgroup
 constexpr int QNT = 64;       // query rows: one thread each
 constexpr int MAX_Q = 1 << 22;
-constexpr int DEFAULT_CHUNK = 1 << 16;
 
 using detm::addf;
 using detm::mulf;
@@ -57,69 +57,11 @@ using rowsel::NONE;   // above every composite of a finite distance
 using rowsel::select_smallest;
 using rowsel::SelectLds;
 using rowsel::SNT;
+using rowsel::write_row;
 
-// orderable's inverse on distances: the only zero a distance takes is -0.0f (simbatch.hip)
-__device__ __forceinline__ float dist_of_key(uint32_t key) {
-  if (key == 0x80000000u) return __uint_as_float(0x80000000u);
-  return __uint_as_float((key & 0x80000000u) ? (key & 0x7FFFFFFFu) : ~key);
-}
-
-__device__ __forceinline__ float inv_norm(float ss) { return 1.f / sqrtf(fmaxf(ss, 1e-12f)); }
-
-// A 128 x 32 tile of z into LDS, zeros outside [0, rows) x [0, K) (simbatch.hip's stage_tile).
-__device__ __forceinline__ void stage_tile(float (*tile)[KS + 1], const float *__restrict__ z, int rows,
-                                           int K, int r0, int k0) {
-  static_assert(NR % KS == 0, "a thread keeps its column: step u holds rows u * NR / KS + tid / KS");
-  const int c = threadIdx.x % KS, rq = threadIdx.x / KS;
-  const bool col_ok = k0 + c < K;
-  float x[KS];
-#pragma unroll
-  for (int u = 0; u < KS; ++u) {
-    const int r = u * (NR / KS) + rq;
-    const bool ok = col_ok && r0 + r < rows;
-    const float v = z[ok ? (int64_t)(r0 + r) * K + k0 + c : 0];
-    x[u] = ok ? v : 0.f;
-  }
-#pragma unroll
-  for (int u = 0; u < KS; ++u) tile[u * (NR / KS) + rq][c] = x[u];
-}
-
-// rows of z -> index rows [n0, n0 + rows): n [.][Kp] and nT [Kp][caps]
-__global__ __launch_bounds__(NR) void put_rows_kernel(const float *__restrict__ z, int rows, int K, int Kp,
-                                                      int caps, int n0, float *__restrict__ n,
-                                                      float *__restrict__ nT) {
-  __shared__ float tile[NR][KS + 1];
-  const int tid = threadIdx.x;
-  const int r0 = blockIdx.x * NR, row = r0 + tid;
-  float ss = 0.f;
-  for (int k0 = 0; k0 < Kp; k0 += KS) {
-    __syncthreads();  // the previous stage's readers are done
-    stage_tile(tile, z, rows, K, r0, k0);
-    __syncthreads();
-    const int kc = min(KS, K - k0);
-    for (int c = 0; c < kc; ++c) {
-      const float x = tile[tid][c];
-      ss = addf(ss, mulf(x, x));
-    }
-  }
-  const float inv = inv_norm(ss);
-  for (int k0 = 0; k0 < Kp; k0 += KS) {
-    __syncthreads();
-    stage_tile(tile, z, rows, K, r0, k0);
-    __syncthreads();
-#pragma unroll 8
-    for (int c = 0; c < KS; ++c) {
-      const float v = mulf(tile[tid][c], inv);
-      tile[tid][c] = v;
-      if (row < rows) nT[(int64_t)(k0 + c) * caps + n0 + row] = v;
-    }
-    __syncthreads();
-    for (int t = tid; t < NR * KS; t += NR) {
-      const int r = t / KS, c = t % KS;
-      if (r0 + r < rows) n[(int64_t)(n0 + r0 + r) * Kp + k0 + c] = tile[r][c];
-    }
-  }
-}
+using cosine::dist_of_key;
+using cosine::inv_norm;
+using cosine::k_pad;
 
 // Query r (one workgroup each): the index row qid[r] (0 <= qid[r] < N), else the raw embedding
 // zq[r] (a negative or absent id, zq given), else none.
@@ -162,67 +104,28 @@ __global__ __launch_bounds__(DNT, 4) void dist_chunk_kernel(const float *__restr
                                                             int cl, int Kp, int Q, int pitch,
                                                             uint32_t *__restrict__ keys) {
   constexpr int TR = 16 * RM;
-  constexpr int F4 = KS / 4, RS = DNT / F4;  // float4 per query row, query rows per step
-  __shared__ __attribute__((aligned(16))) float wsm[KS][TC];
-  __shared__ __attribute__((aligned(16))) float hsm[TR][KS];
   const int tid = threadIdx.x;
   const int tx = tid & 15, ty = tid >> 4;
   const int nb = blockIdx.x * TC;  // first cube of the tile, inside the chunk
   const int rb = blockIdx.y * TR;  // first query of the tile
-  float acc[RM][4];
-#pragma unroll
-  for (int j = 0; j < RM; ++j)
-#pragma unroll
-    for (int e = 0; e < 4; ++e) acc[j][e] = 0.f;
-  // the rows this thread stages are RS rows of qn apart: one pointer, and a bit per row that is
-  // inside Q and a query
-  const float *qbase = qn + (int64_t)(rb + tid / F4) * Kp + 4 * (tid % F4);
+  // A thread stages local rows lr0 + RS * i at k offset kq: one pointer, the distance to it uniform
+  // (a multiple of RS rows and the stage's first k), and a bit per row that is inside Q and a query
+  const int lr0 = tid / dottile::F4, kq = 4 * (tid % dottile::F4);
+  const float *qbase = qn + (int64_t)(rb + lr0) * Kp + kq;
   uint32_t qmask = 0u;
 #pragma unroll
-  for (int i = 0; i < TR / RS; ++i) {
-    const int gr = rb + tid / F4 + RS * i;
+  for (int i = 0; i < TR / dottile::RS; ++i) {
+    const int gr = rb + lr0 + dottile::RS * i;
     if (gr < Q && qok[gr] != 0) qmask |= 1u << i;
   }
-
-  for (int k0 = 0; k0 < Kp; k0 += KS) {
-    __syncthreads();  // the previous stage's readers are done
-    {
-      const int c = tid & 63, gn = nb + c;
-      const float *Wp = nT + ((int64_t)k0 + (tid >> 6)) * caps + c0 + gn;
-      float w[KS / 4];
-#pragma unroll
-      for (int i = 0; i < KS / 4; ++i) w[i] = gn < cl ? Wp[(int64_t)(4 * i) * caps] : 0.f;
-      float4 h[TR / RS];
-#pragma unroll
-      for (int i = 0; i < TR / RS; ++i)
-        h[i] = (qmask >> i) & 1u ? *reinterpret_cast<const float4 *>(qbase + (int64_t)(RS * i) * Kp + k0)
-                                 : make_float4(0.f, 0.f, 0.f, 0.f);
-#pragma unroll
-      for (int i = 0; i < KS / 4; ++i) wsm[4 * i + (tid >> 6)][c] = w[i];
-#pragma unroll
-      for (int i = 0; i < TR / RS; ++i)
-        *reinterpret_cast<float4 *>(&hsm[tid / F4 + RS * i][4 * (tid % F4)]) = h[i];
-    }
-    __syncthreads();
-#pragma unroll 2
-    for (int k4 = 0; k4 < KS / 4; ++k4) {
-      float4 w[4];
-#pragma unroll
-      for (int kk = 0; kk < 4; ++kk) w[kk] = *reinterpret_cast<const float4 *>(&wsm[4 * k4 + kk][4 * tx]);
-#pragma unroll
-      for (int j = 0; j < RM; ++j) {
-        const float4 h = *reinterpret_cast<const float4 *>(&hsm[ty * RM + j][4 * k4]);
-        const float hk[4] = {h.x, h.y, h.z, h.w};
-#pragma unroll
-        for (int kk = 0; kk < 4; ++kk) {
-          acc[j][0] = addf(acc[j][0], mulf(hk[kk], w[kk].x));
-          acc[j][1] = addf(acc[j][1], mulf(hk[kk], w[kk].y));
-          acc[j][2] = addf(acc[j][2], mulf(hk[kk], w[kk].z));
-          acc[j][3] = addf(acc[j][3], mulf(hk[kk], w[kk].w));
-        }
-      }
-    }
-  }
+  const int gn = nb + (tid & 63);
+  const auto dot = dottile::run<RM, false>(
+      Kp, caps, [=](int k) { return gn < cl ? nT + (int64_t)k * caps + c0 + gn : nullptr; },
+      [=](int lr, int k) {
+        return (qmask >> ((lr - lr0) / dottile::RS)) & 1u
+                   ? *reinterpret_cast<const float4 *>(qbase + (int64_t)(lr - lr0) * Kp + (k - kq))
+                   : dottile::zero4();
+      });
 
   const int n0 = nb + 4 * tx;
   if (n0 >= cl) return;
@@ -232,7 +135,7 @@ __global__ __launch_bounds__(DNT, 4) void dist_chunk_kernel(const float *__restr
     if (gr >= Q) continue;
     uint32_t key[4];
 #pragma unroll
-    for (int e = 0; e < 4; ++e) key[e] = orderable(-acc[j][e]);
+    for (int e = 0; e < 4; ++e) key[e] = orderable(-dot.sum[j][e]);
     // pitch % 64 == 0 and cl <= pitch: 16-B aligned, and the pad behind cl is this row's own
     *reinterpret_cast<uint4 *>(keys + (int64_t)gr * pitch + n0) = make_uint4(key[0], key[1], key[2], key[3]);
   }
@@ -246,18 +149,6 @@ struct ChunkItem {  // key << 32 | cube position inside the chunk; the skipped c
     return j == skip ? NONE : cmp;
   }
 };
-// The first `want` entries of s.sel as a result row, then the -1 / 0.f tail.
-__device__ __forceinline__ void write_row(const SelectLds &s, int want, int k, int32_t *oi, float *od) {
-  for (int i = threadIdx.x; i < want; i += SNT) {
-    const uint64_t cmp = s.sel[i];
-    oi[i] = (int32_t)(uint32_t)cmp;
-    od[i] = dist_of_key((uint32_t)(cmp >> 32));
-  }
-  for (int i = max(want, 0) + threadIdx.x; i < k; i += SNT) {
-    oi[i] = -1;
-    od[i] = 0.f;
-  }
-}
 
 // The select kernels are held to 80 allocated SGPRs (72 and the 6 the hardware adds, in steps of
 // 16): at 96 a CU takes one 1,024-thread workgroup instead of two, and these loops, one load in
@@ -285,7 +176,7 @@ CUBESIM_SELECT_KERNEL void select_chunk_kernel(const uint32_t *__restrict__ keys
     return;  // the merge reads nothing of a row that is no query
   }
   if (FINAL) {
-    write_row(s, want, k, out_idx + (int64_t)r * k, out_dist + (int64_t)r * k);  // c0 == 0
+    write_row(s, want, k, out_idx + (int64_t)r * k, out_dist + (int64_t)r * k, dist_of_key);  // c0 == 0
   } else {
     uint64_t *out = cand + ((int64_t)r * chunks + chunk_no) * k;
     // c0 + position < 2^31: the sum stays inside the low word
@@ -311,10 +202,9 @@ CUBESIM_SELECT_KERNEL void merge_rows_kernel(const uint64_t *__restrict__ cand, 
   }
   // chunks * k stays below 2^31: larger counts are refused by the entry
   if (want > 0) select_smallest(s, CandItem{cand + (int64_t)r * chunks * k}, chunks * k, want, (uint32_t)(N - 1));
-  write_row(s, want, k, oi, od);
+  write_row(s, want, k, oi, od, dist_of_key);
 }
 
-int k_pad(int K) { return (int)cdiv(std::max(K, 1), KS) * KS; }
 int cap_pitch(int cap) { return (int)cdiv(std::max(cap, 1), 64) * 64; }
 
 // index: [n cap*Kp][nT Kp*caps]
@@ -335,17 +225,14 @@ IndexLayout index_layout(int cap, int K) {
 
 // workspace: [keys Q*pitch][cand Q*chunks*k][qn Q*Kp][qok Q], pitch = the chunk, or N rounded up to
 // 64 where that is less: it grows with Q * chunk and Q * k * chunks, never with Q * N
-struct SearchWs {
+struct SearchWs : rowsel::ChunkPlan {
   size_t qn, qok, keys, cand, total;
-  int Kp, chunk, pitch, chunks;
+  int Kp;
 };
 SearchWs search_ws(int N, int K, int Q, int k, int chunk) {
-  SearchWs w;
-  const size_t q = (size_t)std::max(Q, 1), n = (size_t)std::max(N, 1);
+  SearchWs w{rowsel::chunk_plan(N, chunk)};
+  const size_t q = (size_t)std::max(Q, 1);
   w.Kp = k_pad(K);
-  w.chunk = chunk > 0 ? chunk : DEFAULT_CHUNK;
-  w.pitch = (int)std::min<size_t>((size_t)w.chunk, (size_t)cdiv((int64_t)n, 64) * 64);
-  w.chunks = (int)cdiv((int64_t)n, w.chunk);
   size_t o = 0;
   w.keys = o, o += align256(q * w.pitch * sizeof(uint32_t));
   w.cand = o, o += align256(q * (size_t)w.chunks * (size_t)std::max(k, 1) * sizeof(uint64_t));
@@ -371,17 +258,15 @@ extern "C" int cc_cube_index_put(void *index, int32_t cap, int32_t K, int32_t n0
                                  const float *z, void *stream) {
   CC_REQUIRE(index && z, "cc_cube_index_put: null pointer");
   CC_REQUIRE(((uintptr_t)index & 255) == 0, "cc_cube_index_put: index must be 256-byte aligned");
-  CC_REQUIRE(cap >= 1 && cap <= 0x7FFFFFFF - 64 && K >= 1 && K <= 0x7FFFFFFF - KS,
+  CC_REQUIRE(cap >= 1 && cap <= 0x7FFFFFFF - 64 && K >= 1 && K <= 0x7FFFFFFF - dottile::KS,
              "cc_cube_index_put: bad cap/K");
   CC_REQUIRE(n0 >= 0 && rows >= 0 && (int64_t)n0 + rows <= cap,
              "cc_cube_index_put: rows [n0, n0 + rows) must lie inside [0, cap)");
   if (rows == 0) return CC_OK;
   const IndexLayout x = index_layout(cap, K);
   char *base = (char *)index;
-  hipLaunchKernelGGL(put_rows_kernel, dim3((unsigned)cdiv(rows, NR)), dim3(NR), 0, as_stream(stream), z,
-                     rows, K, x.Kp, x.caps, n0, (float *)(base + x.n), (float *)(base + x.nT));
-  CC_LAUNCH_CHECK("put_rows_kernel");
-  return CC_OK;
+  return cc::normalise_rows_launch(z, rows, K, x.Kp, x.caps, n0, (float *)(base + x.n),
+                                   (float *)(base + x.nT), as_stream(stream));
 }
 
 extern "C" int32_t cc_cube_neighbours_max_k(void) { return MAX_K; }
@@ -395,7 +280,7 @@ extern "C" int cc_cube_neighbours(const void *index, int32_t cap, int32_t N, int
                                   int32_t chunk, void *ws, int32_t *out_idx, float *out_dist,
                                   void *stream) {
   CC_REQUIRE(index && ws && out_idx && out_dist, "cc_cube_neighbours: null pointer");
-  CC_REQUIRE(cap >= 1 && cap <= 0x7FFFFFFF - 64 && K >= 1 && K <= 0x7FFFFFFF - KS,
+  CC_REQUIRE(cap >= 1 && cap <= 0x7FFFFFFF - 64 && K >= 1 && K <= 0x7FFFFFFF - dottile::KS,
              "cc_cube_neighbours: bad cap/K");
   CC_REQUIRE(N >= 1 && N <= cap, "cc_cube_neighbours: N must be 1..cap");
   CC_REQUIRE(Q >= 0 && Q <= MAX_Q, "cc_cube_neighbours: Q outside 0..2^22");

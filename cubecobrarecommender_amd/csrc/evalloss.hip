@@ -2,12 +2,12 @@
 // and the categorical-accuracy prediction of R rows, on the logits that recommend computes.
 //
 // The chain: target bitmasks, cc::infer_h3_launch on x (h3 is exactly recommend's), then
-//   loss_tile_kernel : out_tile_kernel's tile (recbatch.hip: 64 cards x 16*RM rows, K staged
-//                      through LDS, the same pinned fp32 accumulate, restated here so that
-//                      recbatch.hip compiles to what it did) with another epilogue: instead of a
-//                      sort key per card it reduces, per row of the tile, the fp64 loss terms of the
-//                      tile's 64 cards and the first maximum of p'.  One double, one float and one
-//                      int per (tile, row) go to the workspace; nothing of size R x V is written.
+//   loss_tile_kernel : out_tile_kernel's tile (recbatch.hip: 64 cards x 16*RM rows, its copy of the
+//                      dot-product tile's loop) with another epilogue:
+//                      instead of a sort key per card it reduces, per row of the tile, the fp64
+//                      loss terms of the tile's 64 cards and the first maximum of p'.  One double,
+//                      one float and one int per (tile, row) go to the workspace; nothing of size
+//                      R x V is written.
 //   loss_rows_kernel : one thread per row adds the tile partials in ascending tile order, divides
 //                      by V and keeps the first maximum.
 // Pinned arithmetic (tests/eval_loss_ref.py restates it bit for bit):
@@ -22,24 +22,14 @@
 //         within a lane, across the butterfly and across tiles
 #include "common.hpp"
 #include "detmath.hpp"
-#include "topn_tiles.hpp"
-
-namespace cc {
-int param_offsets(int V, int d, int64_t *off, int64_t *size, int64_t *total, int64_t *main_total);
-// infer.hip
-int infer_check_d(int d, const char *who);
-int infer_gather_cap(int max_n);
-int infer_h3_launch(const float *params, int V, int d, int R, const int32_t *row_ptr,
-                    const int32_t *idx, int max_n, float *part, float *zlat, float *h3,
-                    hipStream_t s);
-}  // namespace cc
+#include "dottile.hpp"
+#include "infer.hpp"
 
 namespace {
 
-constexpr int KCH = 64;   // dot chunk (pinned)
-constexpr int KS = 32;    // k per LDS stage of the output tile
-constexpr int TC = 64;    // cards per output tile
-constexpr int ONT = 256;  // output-tile workgroup: 16 card groups x 16 row groups
+constexpr int KCH = dottile::KCH, KS = dottile::KS;  // the tile's constants (dottile.hpp)
+constexpr int TC = dottile::TC;   // cards per output tile
+constexpr int ONT = dottile::NT;  // output-tile workgroup
 // Eigen scalar_logistic_op<float>: exactly 1 from here on (metrics.hip)
 constexpr float SIG_SAT = 15.7243833541870117f;
 
@@ -60,22 +50,6 @@ __device__ __forceinline__ double bce_term(float z, bool y) {
   const double l = detm::det_log(1.0 + detm::det_exp(-az));
   const double a = m - zy;
   return a + l;
-}
-
-// row_bits_kernel's rule (recbatch.hip) on the target lists: one workgroup per row clears the
-// row's mask and sets it from the row's ids; ids outside [0, V) are ignored
-__global__ __launch_bounds__(256) void tgt_bits_kernel(const int32_t *__restrict__ tgt_ptr,
-                                                       const int32_t *__restrict__ tgt, int V,
-                                                       int VW, uint32_t *__restrict__ bits) {
-  const int r = blockIdx.x;
-  uint32_t *b = bits + (int64_t)r * VW;
-  for (int i = threadIdx.x; i < VW; i += 256) b[i] = 0u;
-  __syncthreads();
-  const int beg = tgt_ptr[r], end = tgt_ptr[r + 1];
-  for (int i = beg + (int)threadIdx.x; i < end; i += 256) {
-    const int j = tgt[i];
-    if ((uint32_t)j < (uint32_t)V) atomicOr(&b[j >> 5], 1u << (j & 31));
-  }
 }
 
 // tile_loss / tile_p / tile_i: [tiles][R], tile-major so that loss_rows_kernel reads coalesced
@@ -267,8 +241,8 @@ extern "C" int cc_recommend_batch_loss_fp32(const float *params, int32_t V, int3
   double *tl = (double *)(base + w.tloss);
   float *tp = (float *)(base + w.tp);
   int32_t *ti = (int32_t *)(base + w.ti);
-  hipLaunchKernelGGL(tgt_bits_kernel, dim3(R), dim3(256), 0, s, tgt_ptr, tgt, V, w.VW, bits);
-  CC_LAUNCH_CHECK("tgt_bits_kernel");
+  // the targets' masks by the rule of the cube masks: ids outside [0, V) are ignored
+  if (int rc = cc::row_bits_launch(tgt_ptr, tgt, R, V, w.VW, bits, s)) return rc;
   if (int rc = cc::infer_h3_launch(params, V, d, R, row_ptr, idx, max_n, (float *)(base + w.part),
                                    (float *)(base + w.zlat), h3, s))
     return rc;

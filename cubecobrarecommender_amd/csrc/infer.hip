@@ -19,6 +19,7 @@
 //                           partials meet in LDS and wave 0 adds them in order + sigmoid.
 #include "common.hpp"
 #include "detmath.hpp"
+#include "infer.hpp"
 #include "topn_tiles.hpp"
 
 namespace {
@@ -212,9 +213,8 @@ int tower_lds_bytes(int d) {
 
 }  // namespace
 
-// layout helper implemented in api.cpp
+// topn.hip
 namespace cc {
-int param_offsets(int V, int d, int64_t *off, int64_t *size, int64_t *total, int64_t *main_total);
 int topn_launch(const float *probs, int V, const int32_t *cube_idx, int n, int amount,
                 int32_t *additions, int32_t *n_add, float *add_vals, float *cut_vals,
                 int32_t *order, void *ws, hipStream_t stream);

@@ -10,7 +10,7 @@
 //     SHIFTED by one id (ids 32c+1 .. 32c+32), and only chunk cj is summed per row: its other ids
 //     in order, then the next chunk's first id.  The same additions in the same order.
 //   The output layer is needed at chosen cards only: rows x targets dots against gathered columns
-//     of Wo, in out_tile_kernel's pinned 64-wide chunks.
+//     of Wo, in the forward pass's pinned 64-wide chunks.
 //   loo_partials_kernel: one workgroup per (cube, chunk): 33 rows of W1 loaded once, the chunk's
 //                        partial (gather_partials_kernel's additions) and its shifted partial.
 //   loo_e1_kernel      : one workgroup per derived row: the own chunk (all loads before the first
@@ -18,34 +18,26 @@
 //   tower_kernel       : infer.hip's, unchanged, fed e1 as one-chunk partials (cap = 1): 0 + x is
 //                        exact and a total summed from +0 is never -0.
 //   loo_tile_kernel    : 32 derived rows x 64 target cards per tile.  A row tile is cut into runs
-//                        of rows of one cube; a run meets its cube's targets with the gathered
-//                        Wo columns [32 k][64 targets] and h3 [32 rows][32 k] staged in LDS.
+//                        of rows of one cube; a run meets its cube's targets in the shared
+//                        dot-product tile (dottile.hpp) with gathered Wo columns.
 //                        Self mode (no targets): only base rows take part, their targets are the
 //                        cube's own cards (today's cut values).
 //   loo_self_kernel    : self mode's derived rows: one dot per row against the column of its
 //                        left-out card, one lane per 64-wide chunk.  Nothing n x n exists.
 #include "common.hpp"
 #include "detmath.hpp"
-
-namespace cc {
-int param_offsets(int V, int d, int64_t *off, int64_t *size, int64_t *total, int64_t *main_total);
-// infer.hip
-int infer_check_d(int d, const char *who);
-int infer_gather_cap(int max_n);
-int infer_towers_launch(const float *params, int V, int d, int R, const int32_t *one_ptr,
-                        const float *e1, float *zlat, float *h3, hipStream_t s);
-}  // namespace cc
+#include "dottile.hpp"
+#include "infer.hpp"
 
 namespace {
 
 constexpr int GCH = 32;   // gather chunk (pinned)
 constexpr int GNT = 128;  // gather workgroup
-constexpr int KCH = 64;   // dot chunk (pinned)
-constexpr int KS = 32;    // k per LDS stage of the output tile
-constexpr int TC = 64;    // targets per output tile
-constexpr int RM = 2;     // rows per thread of the output tile
+constexpr int KCH = dottile::KCH;  // dot chunk (pinned)
+constexpr int TC = dottile::TC;    // targets per output tile
+constexpr int RM = 2;              // rows per thread of the output tile
 constexpr int TR = 16 * RM;
-constexpr int ONT = 256;  // output-tile workgroup: 16 target groups x 16 row groups
+constexpr int ONT = dottile::NT;   // output-tile workgroup
 constexpr int SR = 16;    // rows per workgroup of loo_self_kernel
 
 using detm::addf;
@@ -53,11 +45,7 @@ using detm::mulf;
 __device__ __forceinline__ float4 add4(float4 a, float4 b) {
   return make_float4(addf(a.x, b.x), addf(a.y, b.y), addf(a.z, b.z), addf(a.w, b.w));
 }
-__device__ __forceinline__ float4 zero4() { return make_float4(0.f, 0.f, 0.f, 0.f); }
-// an id outside [0, V) is never used as an index: it travels as -1
-__device__ __forceinline__ int32_t card_or_none(int32_t id, int V) {
-  return (uint32_t)id < (uint32_t)V ? id : -1;
-}
+using dottile::zero4;
 
 // What a derived row names.  ok = 0: a cube outside [0, n_cubes), a position outside [-1, n) or a
 // cube longer than the partials' pitch; such a row indexes nothing and writes no result.
@@ -183,8 +171,6 @@ __global__ __launch_bounds__(ONT) void loo_tile_kernel(
     int rows, const int32_t *__restrict__ row_cube, const int32_t *__restrict__ row_pos,
     const int32_t *__restrict__ tgt_ptr, const int32_t *__restrict__ tgt,
     const int32_t *__restrict__ out_ptr, float *__restrict__ out) {
-  __shared__ __attribute__((aligned(16))) float wsm[KS][TC];
-  __shared__ __attribute__((aligned(16))) float hsm[TR][KS];
   __shared__ int32_t s_cube[TR], s_act[TR], s_t[TC];
   const int tid = threadIdx.x;
   const int tx = tid & 15, ty = tid >> 4;
@@ -226,59 +212,17 @@ __global__ __launch_bounds__(ONT) void loo_tile_kernel(
       const int t0 = ct * TC;
       __syncthreads();  // the previous tile's readers of s_t are done
       if (tid < TC) s_t[tid] = t0 + tid < T ? card_or_none(tl[t0 + tid], V) : -1;
-      float tot[RM][4], acc[RM][4];
-#pragma unroll
-      for (int j = 0; j < RM; ++j)
-#pragma unroll
-        for (int e = 0; e < 4; ++e) tot[j][e] = acc[j][e] = 0.f;
-
-      for (int k0 = 0; k0 < d; k0 += KS) {
-        __syncthreads();  // the previous stage's readers are done (and s_t is written)
-        {
-          const int n = tid & 63, card = s_t[n];
-          const float *Wp = Wo + ((int64_t)k0 + (tid >> 6)) * V + (card >= 0 ? card : 0);
-          float w[KS / 4];
-#pragma unroll
-          for (int i = 0; i < KS / 4; ++i) w[i] = card >= 0 ? Wp[(int64_t)(4 * i) * V] : 0.f;
-          constexpr int Q = KS / 4;  // float4 per row; ONT / Q == TR: one float4 per thread
-          static_assert(ONT / Q == TR, "one h3 float4 per thread and stage");
-          const int lr = tid / Q;
-          const bool in = lr >= r0 && lr < r1 && s_act[lr];
-          const float4 h = in ? *reinterpret_cast<const float4 *>(h3 + (int64_t)(rb + lr) * d + k0 + 4 * (tid % Q))
-                              : zero4();
-#pragma unroll
-          for (int i = 0; i < KS / 4; ++i) wsm[4 * i + (tid >> 6)][n] = w[i];
-          *reinterpret_cast<float4 *>(&hsm[lr][4 * (tid % Q)]) = h;
-        }
-        __syncthreads();
-#pragma unroll 2
-        for (int k4 = 0; k4 < KS / 4; ++k4) {
-          float4 w[4];
-#pragma unroll
-          for (int kk = 0; kk < 4; ++kk) w[kk] = *reinterpret_cast<const float4 *>(&wsm[4 * k4 + kk][4 * tx]);
-#pragma unroll
-          for (int j = 0; j < RM; ++j) {
-            const float4 h = *reinterpret_cast<const float4 *>(&hsm[ty * RM + j][4 * k4]);
-            const float hk[4] = {h.x, h.y, h.z, h.w};
-#pragma unroll
-            for (int kk = 0; kk < 4; ++kk) {
-              acc[j][0] = addf(acc[j][0], mulf(hk[kk], w[kk].x));
-              acc[j][1] = addf(acc[j][1], mulf(hk[kk], w[kk].y));
-              acc[j][2] = addf(acc[j][2], mulf(hk[kk], w[kk].z));
-              acc[j][3] = addf(acc[j][3], mulf(hk[kk], w[kk].w));
-            }
-          }
-        }
-        if ((k0 + KS) % KCH == 0) {  // a pinned chunk ends: its partial joins the total
-#pragma unroll
-          for (int j = 0; j < RM; ++j)
-#pragma unroll
-            for (int e = 0; e < 4; ++e) {
-              tot[j][e] = addf(tot[j][e], acc[j][e]);
-              acc[j][e] = 0.f;
-            }
-        }
-      }
+      // (the tile's first barrier is behind this write and before its first read of s_t)
+      const auto dot = dottile::run<RM, true>(
+          d, V,
+          [=](int k) {
+            const int card = s_t[tid & 63];
+            return card >= 0 ? Wo + (int64_t)k * V + card : nullptr;
+          },
+          [=](int lr, int k) {
+            const bool in = lr >= r0 && lr < r1 && s_act[lr];
+            return in ? *reinterpret_cast<const float4 *>(h3 + (int64_t)(rb + lr) * d + k) : zero4();
+          });
 
 #pragma unroll
       for (int j = 0; j < RM; ++j) {
@@ -290,7 +234,7 @@ __global__ __launch_bounds__(ONT) void loo_tile_kernel(
           const int t = t0 + 4 * tx + e;
           if (t >= T || t >= span) continue;
           const int card = s_t[4 * tx + e];
-          out[(int64_t)ob + t] = card >= 0 ? detm::det_sigmoid32(addf(tot[j][e], bo[card])) : 0.f;
+          out[(int64_t)ob + t] = card >= 0 ? detm::det_sigmoid32(addf(dot.sum[j][e], bo[card])) : 0.f;
         }
       }
     }

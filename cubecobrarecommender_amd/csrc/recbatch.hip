@@ -5,18 +5,11 @@
 // workgroup per row) for h3 [R, d]; the rest is here:
 //   row_bits_kernel : one workgroup per row clears the row's cube bitmask and sets it from the
 //                     row's ids (nothing in the workspace survives from an earlier call).
-//   out_tile_kernel : one workgroup per tile of 16*RM rows x 64 cards.  K is streamed: 32 k of
-//                     Wo [32 k][64 cards] and of h3 [rows][32 k] are staged in LDS at a time and
-//                     shared by all the tile's rows (24 KB at 128 rows: four workgroups per CU); a
-//                     thread owns RM rows x 4 cards, one chunk accumulator and one running total
-//                     each, so any d fits.  The compiler pairs the cards into v_pk_mul_f32 /
-//                     v_pk_add_f32.  Arithmetic per (row, card) is out_kernel's, in the pinned
-//                     64-wide chunks: acc = acc + h[k]*W[k][n]
-//                     from 0 inside a chunk, chunk partials added in order from 0, + bo[n],
-//                     det_sigmoid32; multiply and add separately rounded (no contraction, so no
-//                     MFMA).  Writes the sort key of every card, the probability of every cube
-//                     card into its cut-value slot (binary search of the row's sorted ids), and
-//                     the probabilities only on request.
+//   out_tile_kernel : one workgroup per tile of 16*RM rows x 64 cards: the dot-product tile of
+//                     DESIGN.md 4.10 in out_kernel's pinned 64-wide chunks (its own copy of
+//                     dottile.hpp's loop: see there), so any d fits, then + bo[n], det_sigmoid32.  Writes the sort key of every card,
+//                     the probability of every cube card into its cut-value slot (binary search
+//                     of the row's sorted ids), and the probabilities only on request.
 //   topn_rows_kernel: one workgroup per row.  The composite (key' << 32 | card) is unique, so
 //                     the want largest are a radix SELECT of the want-th largest composite (10-bit
 //                     digits from the top, LDS histograms, suffix scan; stops as soon as the
@@ -43,31 +36,23 @@
 // complete.hip runs it pass after pass; the two select entries are that call behind their checks.
 #include "common.hpp"
 #include "detmath.hpp"
+#include "dottile.hpp"
+#include "infer.hpp"
 #include "rowsort.hpp"
 #include "topn_tiles.hpp"
 
-namespace cc {
-int param_offsets(int V, int d, int64_t *off, int64_t *size, int64_t *total, int64_t *main_total);
-// infer.hip
-int infer_check_d(int d, const char *who);
-int infer_gather_cap(int max_n);
-int infer_h3_launch(const float *params, int V, int d, int R, const int32_t *row_ptr,
-                    const int32_t *idx, int max_n, float *part, float *zlat, float *h3,
-                    hipStream_t s);
-}  // namespace cc
-
 namespace {
 
-constexpr int KCH = 64;      // dot chunk (pinned)
-constexpr int KS = 32;       // k per LDS stage of the output tile
-constexpr int TC = 64;       // cards per output tile
-constexpr int ONT = 256;     // output-tile workgroup: 16 card groups x 16 row groups
+constexpr int KCH = dottile::KCH, KS = dottile::KS;  // the tile's constants (dottile.hpp)
+constexpr int TC = dottile::TC;   // cards per output tile
+constexpr int ONT = dottile::NT;  // output-tile workgroup
 constexpr int SNT = 1024;    // top-N workgroup
 constexpr int MAX_AMOUNT = 2048;  // survivors sorted in LDS
 
 using detm::addf;
 using detm::mulf;
 
+// (also evalloss.hip's target masks, through cc::row_bits_launch: ids outside [0, V) are ignored)
 __global__ __launch_bounds__(256) void row_bits_kernel(const int32_t *__restrict__ row_ptr,
                                                        const int32_t *__restrict__ idx, int V,
                                                        int VW, uint32_t *__restrict__ bits) {
@@ -139,7 +124,8 @@ __global__ __launch_bounds__(ONT) void out_tile_kernel(
     const uint32_t *__restrict__ bits, int VW, uint32_t *__restrict__ keys, int Vs,
     float *__restrict__ cut_vals, float *__restrict__ probs, const uint32_t *__restrict__ excl) {
   constexpr int TR = 16 * RM;
-  // LDS stage: KS of a chunk's 64 k at a time (the chunk accumulator runs across its stages), so
+  // dottile::run<RM, true>'s loop, statement for statement but for the order of the two LDS reads
+  // (DESIGN.md 4.10).  LDS stage: KS of a chunk's 64 k at a time (the chunk accumulator runs across its stages), so
   // that four workgroups fit a CU
   __shared__ __attribute__((aligned(16))) float wsm[KS][TC];
   __shared__ __attribute__((aligned(16))) float hsm[TR][KS];
@@ -612,6 +598,13 @@ extern "C" size_t cc_recommend_batch_ws_size(int32_t V, int32_t d, int32_t R, in
   return batch_ws(V, d, R, max_n).total + 256;
 }
 
+int cc::row_bits_launch(const int32_t *row_ptr, const int32_t *idx, int R, int V, int VW,
+                        uint32_t *bits, hipStream_t s) {
+  hipLaunchKernelGGL(row_bits_kernel, dim3(R), dim3(256), 0, s, row_ptr, idx, V, VW, bits);
+  CC_LAUNCH_CHECK("row_bits_kernel");
+  return CC_OK;
+}
+
 // The launches all entries share: row masks, h3, then the output layer, which leaves every row's
 // sort keys in the workspace, its cut values and (on request) its probabilities.  pl: a pooled
 // call's arguments, or null; *n_cand then points at the rows' candidate counts, or is null.
@@ -633,9 +626,8 @@ static int batch_keys_launch(const float *params, int V, int d, int R, const int
                        pl->n_pools, pl->pool_of_row, bits, (uint32_t *)(base + p.excl),
                        (int32_t *)(base + p.ncand));
     CC_LAUNCH_CHECK("row_mask_kernel");
-  } else {
-    hipLaunchKernelGGL(row_bits_kernel, dim3(R), dim3(256), 0, s, row_ptr, idx, V, w.VW, bits);
-    CC_LAUNCH_CHECK("row_bits_kernel");
+  } else if (int rc = cc::row_bits_launch(row_ptr, idx, R, V, w.VW, bits, s)) {
+    return rc;
   }
   if (int rc = cc::infer_h3_launch(params, V, d, R, row_ptr, idx, max_n, (float *)(base + w.part),
                                    (float *)(base + w.zlat), h3, s))

@@ -1,6 +1,7 @@
 // The exact k-smallest select of the chunked searches (cubesim.hip, audience.hip): one 1,024-thread
 // workgroup per row picks the `want` smallest 64-bit composites (key << 32 | id, unique per row) of
-// a row of items and leaves them ascending in LDS.  Device only; built on rowsort.hpp.
+// a row of items and leaves them ascending in LDS.  Built on rowsort.hpp; device code but for
+// chunk_plan, the host's split of the corpus.
 //
 // The scheme both searches share: the corpus is walked in chunks, a chunk's min(k, population)
 // smallest composites are kept as the row's candidates with global ids, and the same select over
@@ -16,6 +17,21 @@ constexpr int SNT = 1024;     // select workgroup
 constexpr int MAX_K = 1024;   // results per row
 constexpr int MAX_SEL = 2048; // survivors sorted in LDS
 constexpr uint64_t NONE = ~0ull;  // no candidate: above every composite of a real key
+constexpr int DEFAULT_CHUNK = 1 << 16;
+
+// A search's walk over a corpus of N items: chunks of `chunk` items (0: the default), and the key
+// rows' pitch: the chunk, or N rounded up to 64 where that is less.
+struct ChunkPlan {
+  int chunk, pitch, chunks;
+};
+inline ChunkPlan chunk_plan(int N, int chunk) {
+  const int64_t n = N > 1 ? N : 1;
+  ChunkPlan p;
+  p.chunk = chunk > 0 ? chunk : DEFAULT_CHUNK;
+  p.pitch = (int)(p.chunk < cdiv(n, 64) * 64 ? p.chunk : cdiv(n, 64) * 64);
+  p.chunks = (int)cdiv(n, p.chunk);
+  return p;
+}
 
 // The LDS of one select (select_rows_kernel's).
 struct SelectLds {
@@ -87,6 +103,22 @@ __device__ __forceinline__ void select_smallest(SelectLds &s, const Item &item, 
   for (int i = cnt + tid; i < P; i += SNT) s.sel[i] = NONE;
   __syncthreads();
   rowsort::bitonic_sort<SNT>(P, rowsort::CmpSwapU64<false>{s.sel});
+}
+
+// The first `want` entries of s.sel as a result row (the composite's id, value_of_key of its key),
+// then the -1 / 0.f tail up to k.
+template <class ValueOfKey>
+__device__ __forceinline__ void write_row(const SelectLds &s, int want, int k, int32_t *oi, float *ov,
+                                          ValueOfKey value_of_key) {
+  for (int i = threadIdx.x; i < want; i += SNT) {
+    const uint64_t cmp = s.sel[i];
+    oi[i] = (int32_t)(uint32_t)cmp;
+    ov[i] = value_of_key((uint32_t)(cmp >> 32));
+  }
+  for (int i = max(want, 0) + threadIdx.x; i < k; i += SNT) {
+    oi[i] = -1;
+    ov[i] = 0.f;
+  }
 }
 
 // A row's candidates of all chunks, as the chunk selects stored them.

@@ -5,19 +5,18 @@
 // The single-request kernel recomputes both norms for every (query, card) and walks rows at a
 // stride of K floats.  n_j[i] = e_j[i] * inv_j is the very factor it multiplies (qe[i]*invq is
 // n_q[i] of row q), so normalising every card once changes no bit:
-//   normalise_kernel : one thread per card over a tile of 128 rows staged through LDS (pitch 33:
+//   normalise_kernel : one thread per row over a tile of 128 rows staged through LDS (pitch 33:
 //                      coalesced loads, conflict-free row walks).  ss_j in index order,
 //                      inv_j = 1/sqrt(max(ss_j, 1e-12)), then n [V][Kp] (row-major, for the
 //                      queries) and nT [Kp][Vs] (k-major, for the cards); Kp = K rounded up to the
-//                      distance kernel's k stage, the pad written as zeros.
-//   dist_tile_kernel : one workgroup per tile of 16*RM queries x 64 cards (recbatch.hip's
-//                      out_tile_kernel with n for both operands).  32 k of nT [32 k][64 cards] and
-//                      of the queries' rows [queries][32 k] are staged in LDS at a time, so any
-//                      K > 0 fits; a thread owns RM queries x 4 cards, one accumulator each:
-//                      dot = dot + n_q[k]*n_j[k] from +0 in index order.  The pad adds +0 * +0 to
-//                      a sum that is never -0: no bit moves.  Writes the sort key
-//                      orderable(-dot) of every (query, card) and the distances only on request.
-//                      Query ids come from device memory; one outside [0, V) is never an index.
+//                      distance kernel's k stage, the pad written as zeros.  It writes at a row
+//                      offset (0 here): cubesim.hip's puts run it through cc::normalise_rows_launch.
+//   dist_tile_kernel : one workgroup per tile of 16*RM queries x 64 cards: the shared dot-product
+//                      tile (dottile.hpp) with n for both operands and one running
+//                      sum, so any K > 0 fits.  The pad adds +0 * +0 to a sum that is never -0: no
+//                      bit moves.  Writes the sort key orderable(-dot) of every (query, card) and
+//                      the distances only on request.  Query ids come from device memory; one
+//                      outside [0, V) is never an index.
 //   select_rows_kernel: one workgroup per query.  The composite (key << 32 | card) is unique, so
 //                      the N smallest are a radix SELECT of the N-th smallest composite (10-bit
 //                      digits from the top, LDS histograms, prefix scan; stops as soon as the
@@ -34,15 +33,17 @@
 #include <algorithm>
 
 #include "common.hpp"
+#include "cosine.hpp"
 #include "detmath.hpp"
+#include "dottile.hpp"
 #include "rowsort.hpp"
 
 namespace {
 
-constexpr int KS = 32;        // k per LDS stage of the distance tile
-constexpr int TC = 64;        // cards per distance tile
-constexpr int DNT = 256;      // distance-tile workgroup: 16 card groups x 16 query groups
-constexpr int NR = 128;       // normalise: cards per workgroup, one thread each
+constexpr int KS = dottile::KS;   // k per stage of the normalise tile: the distance tile's
+constexpr int TC = dottile::TC;   // cards per distance tile
+constexpr int DNT = dottile::NT;  // distance-tile workgroup
+constexpr int NR = 128;       // normalise: rows per workgroup, one thread each
 constexpr int SNT = 1024;     // select / sort workgroup
 constexpr int MAX_N = 2048;   // survivors sorted in LDS
 constexpr int MAX_Q = 1 << 22;
@@ -52,15 +53,11 @@ constexpr int SPASSES = 4;
 using detm::addf;
 using detm::mulf;
 using rowsort::orderable;  // similarity.hip's sort key
-// its inverse on distances: the only zero a distance takes is -0.0f
-__device__ __forceinline__ float dist_of_key(uint32_t key) {
-  if (key == 0x80000000u) return __uint_as_float(0x80000000u);
-  return __uint_as_float((key & 0x80000000u) ? (key & 0x7FFFFFFFu) : ~key);
-}
+using cosine::dist_of_key;
 
-// A 128 x 32 tile of emb into LDS, zeros outside [0, V) x [0, K): a thread's 32 loads are issued
+// A 128 x 32 tile of z into LDS, zeros outside [0, rows) x [0, K): a thread's 32 loads are issued
 // together (an address that is always valid, the value dropped afterwards), then stored.
-__device__ __forceinline__ void stage_tile(float (*tile)[KS + 1], const float *__restrict__ emb, int V,
+__device__ __forceinline__ void stage_tile(float (*tile)[KS + 1], const float *__restrict__ z, int rows,
                                            int K, int r0, int k0) {
   static_assert(NR % KS == 0, "a thread keeps its column: step u holds rows u * NR / KS + tid / KS");
   const int c = threadIdx.x % KS, rq = threadIdx.x / KS;
@@ -69,47 +66,48 @@ __device__ __forceinline__ void stage_tile(float (*tile)[KS + 1], const float *_
 #pragma unroll
   for (int u = 0; u < KS; ++u) {
     const int r = u * (NR / KS) + rq;
-    const bool ok = col_ok && r0 + r < V;
-    const float v = emb[ok ? (int64_t)(r0 + r) * K + k0 + c : 0];
+    const bool ok = col_ok && r0 + r < rows;
+    const float v = z[ok ? (int64_t)(r0 + r) * K + k0 + c : 0];
     x[u] = ok ? v : 0.f;
   }
 #pragma unroll
   for (int u = 0; u < KS; ++u) tile[u * (NR / KS) + rq][c] = x[u];
 }
 
-__global__ __launch_bounds__(NR) void normalise_kernel(const float *__restrict__ emb, int V, int K,
-                                                       int Kp, int Vs, float *__restrict__ n,
+// rows of z -> rows [0, rows) of n [.][Kp] and columns [0, rows) of nT [Kp][pitch] (a row offset is
+// in the pointers).  One thread per row, so a row's bits do not depend on where a launch starts or ends.
+__global__ __launch_bounds__(NR) void normalise_kernel(const float *__restrict__ z, int rows, int K, int Kp,
+                                                       int pitch, float *__restrict__ n,
                                                        float *__restrict__ nT) {
-#pragma clang fp contract(off)
   __shared__ float tile[NR][KS + 1];
   const int tid = threadIdx.x;
   const int r0 = blockIdx.x * NR, row = r0 + tid;
   float ss = 0.f;
   for (int k0 = 0; k0 < Kp; k0 += KS) {
     __syncthreads();  // the previous stage's readers are done
-    stage_tile(tile, emb, V, K, r0, k0);
+    stage_tile(tile, z, rows, K, r0, k0);
     __syncthreads();
     const int kc = min(KS, K - k0);
     for (int c = 0; c < kc; ++c) {
       const float x = tile[tid][c];
-      ss = ss + x * x;
+      ss = addf(ss, mulf(x, x));
     }
   }
-  const float inv = 1.f / sqrtf(fmaxf(ss, 1e-12f));
+  const float inv = cosine::inv_norm(ss);
   for (int k0 = 0; k0 < Kp; k0 += KS) {
     __syncthreads();
-    stage_tile(tile, emb, V, K, r0, k0);
+    stage_tile(tile, z, rows, K, r0, k0);
     __syncthreads();
 #pragma unroll 8
     for (int c = 0; c < KS; ++c) {
-      const float v = tile[tid][c] * inv;
+      const float v = mulf(tile[tid][c], inv);
       tile[tid][c] = v;
-      if (row < V) nT[(int64_t)(k0 + c) * Vs + row] = v;
+      if (row < rows) nT[(int64_t)(k0 + c) * pitch + row] = v;
     }
     __syncthreads();
     for (int t = tid; t < NR * KS; t += NR) {
       const int r = t / KS, c = t % KS;
-      if (r0 + r < V) n[(int64_t)(r0 + r) * Kp + k0 + c] = tile[r][c];
+      if (r0 + r < rows) n[(int64_t)(r0 + r) * Kp + k0 + c] = tile[r][c];
     }
   }
 }
@@ -122,65 +120,27 @@ __global__ __launch_bounds__(DNT) void dist_tile_kernel(const float *__restrict_
                                                         uint32_t *__restrict__ keys,
                                                         float *__restrict__ dist_all) {
   constexpr int TR = 16 * RM;
-  constexpr int F4 = KS / 4, RS = DNT / F4;  // float4 per query row, query rows per step
-  __shared__ __attribute__((aligned(16))) float wsm[KS][TC];
-  __shared__ __attribute__((aligned(16))) float hsm[TR][KS];
   const int tid = threadIdx.x;
   const int tx = tid & 15, ty = tid >> 4;
   const int nb = blockIdx.x * TC;  // first card of the tile
   const int rb = blockIdx.y * TR;  // first query of the tile
-  float acc[RM][4];
+  // A thread stages local rows lr0 + RS * i at k offset kq: their pointers, null for a row past Q
+  // or a query id outside [0, V)
+  const int lr0 = tid / dottile::F4, kq = 4 * (tid % dottile::F4);
+  const float *qrow[TR / dottile::RS];
 #pragma unroll
-  for (int j = 0; j < RM; ++j)
-#pragma unroll
-    for (int e = 0; e < 4; ++e) acc[j][e] = 0.f;
-  // the rows this thread stages: null for a row past Q or a query id outside [0, V)
-  const float *qrow[TR / RS];
-#pragma unroll
-  for (int i = 0; i < TR / RS; ++i) {
-    const int gr = rb + tid / F4 + RS * i;
+  for (int i = 0; i < TR / dottile::RS; ++i) {
+    const int gr = rb + lr0 + dottile::RS * i;
     const int q = gr < Q ? queries[gr] : -1;
-    qrow[i] = (uint32_t)q < (uint32_t)V ? n + (int64_t)q * Kp + 4 * (tid % F4) : nullptr;
+    qrow[i] = (uint32_t)q < (uint32_t)V ? n + (int64_t)q * Kp + kq : nullptr;
   }
-
-  for (int k0 = 0; k0 < Kp; k0 += KS) {
-    __syncthreads();  // the previous stage's readers are done
-    {
-      const int c = tid & 63, gn = nb + c;
-      const float *Wp = nT + ((int64_t)k0 + (tid >> 6)) * Vs + gn;
-      float w[KS / 4];
-#pragma unroll
-      for (int i = 0; i < KS / 4; ++i) w[i] = gn < V ? Wp[(int64_t)(4 * i) * Vs] : 0.f;
-      float4 h[TR / RS];
-#pragma unroll
-      for (int i = 0; i < TR / RS; ++i)
-        h[i] = qrow[i] ? *reinterpret_cast<const float4 *>(qrow[i] + k0) : make_float4(0.f, 0.f, 0.f, 0.f);
-#pragma unroll
-      for (int i = 0; i < KS / 4; ++i) wsm[4 * i + (tid >> 6)][c] = w[i];
-#pragma unroll
-      for (int i = 0; i < TR / RS; ++i)
-        *reinterpret_cast<float4 *>(&hsm[tid / F4 + RS * i][4 * (tid % F4)]) = h[i];
-    }
-    __syncthreads();
-#pragma unroll 2
-    for (int k4 = 0; k4 < KS / 4; ++k4) {
-      float4 w[4];
-#pragma unroll
-      for (int kk = 0; kk < 4; ++kk) w[kk] = *reinterpret_cast<const float4 *>(&wsm[4 * k4 + kk][4 * tx]);
-#pragma unroll
-      for (int j = 0; j < RM; ++j) {
-        const float4 h = *reinterpret_cast<const float4 *>(&hsm[ty * RM + j][4 * k4]);
-        const float hk[4] = {h.x, h.y, h.z, h.w};
-#pragma unroll
-        for (int kk = 0; kk < 4; ++kk) {
-          acc[j][0] = addf(acc[j][0], mulf(hk[kk], w[kk].x));
-          acc[j][1] = addf(acc[j][1], mulf(hk[kk], w[kk].y));
-          acc[j][2] = addf(acc[j][2], mulf(hk[kk], w[kk].z));
-          acc[j][3] = addf(acc[j][3], mulf(hk[kk], w[kk].w));
-        }
-      }
-    }
-  }
+  const int gn = nb + (tid & 63);
+  const auto dot = dottile::run<RM, false>(
+      Kp, Vs, [=](int k) { return gn < V ? nT + (int64_t)k * Vs + gn : nullptr; },
+      [=](int lr, int k) {
+        const float *row = qrow[(lr - lr0) / dottile::RS];
+        return row ? *reinterpret_cast<const float4 *>(row + (k - kq)) : dottile::zero4();
+      });
 
   const int n0 = nb + 4 * tx;
   if (n0 >= V) return;
@@ -193,7 +153,7 @@ __global__ __launch_bounds__(DNT) void dist_tile_kernel(const float *__restrict_
     uint32_t key[4];
 #pragma unroll
     for (int e = 0; e < 4; ++e) {
-      dd[e] = ok ? -acc[j][e] : 0.f;
+      dd[e] = ok ? -dot.sum[j][e] : 0.f;
       key[e] = orderable(dd[e]);
     }
     uint32_t *kr = keys + (int64_t)gr * Vs + n0;  // Vs % 4 == 0: 16-B aligned, the pad is ours
@@ -358,7 +318,7 @@ struct SimWs {
 SimWs sim_ws(int V, int K, int Q, int N) {
   SimWs w;
   const size_t v = (size_t)std::max(V, 1), q = (size_t)std::max(Q, 1);
-  w.Kp = (int)cdiv(std::max(K, 1), KS) * KS;
+  w.Kp = cosine::k_pad(K);
   w.Vs = (int)((v + 3) & ~(size_t)3);
   w.Vp = (int)((v + 15) & ~(size_t)15);
   size_t o = 0;
@@ -383,6 +343,14 @@ void launch_dist(hipStream_t s, const float *n, const float *nT, int V, int Kp, 
 }
 
 }  // namespace
+
+int cc::normalise_rows_launch(const float *z, int rows, int K, int Kp, int pitch, int n0, float *n,
+                              float *nT, hipStream_t s) {
+  hipLaunchKernelGGL(normalise_kernel, dim3((unsigned)cdiv(rows, NR)), dim3(NR), 0, s, z, rows, K, Kp,
+                     pitch, n + (int64_t)n0 * Kp, nT + n0);
+  CC_LAUNCH_CHECK("normalise_kernel");
+  return CC_OK;
+}
 
 extern "C" int32_t cc_similar_batch_max_n(void) { return MAX_N; }
 
@@ -414,9 +382,7 @@ static int similar_batch_launch(const float *emb, int V, int K, int Q, const int
   float *n = (float *)(base + w.n), *nT = (float *)(base + w.nT);
   uint32_t *keys = (uint32_t *)(base + w.keys);
   if (ev) CC_HIP(hipEventRecord(ev[0], s));
-  hipLaunchKernelGGL(normalise_kernel, dim3((unsigned)cdiv(V, NR)), dim3(NR), 0, s, emb, V, K, w.Kp,
-                     w.Vs, n, nT);
-  CC_LAUNCH_CHECK("normalise_kernel");
+  if (int rc = cc::normalise_rows_launch(emb, V, K, w.Kp, w.Vs, 0, n, nT, s)) return rc;
   if (ev) CC_HIP(hipEventRecord(ev[1], s));
   // queries per tile: 32 / 64 / 128 (the arithmetic per (query, card) does not depend on it)
   if (Q <= 32)

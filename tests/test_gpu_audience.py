@@ -183,6 +183,11 @@ def test_against_the_oracle(V, d, N):
     check_prefix(case_of(V, d, 1029, seed=V), N, (1, 7, 64, 65, 130), seed=N)
 
 
+def test_three_chunks_of_k():
+    """d = 192, T = 65 cards (a second card tile of one) over N = 65 cubes in two chunks of 64."""
+    check_prefix(Case(299, 192, 65, seed=299), 65, (65,), seed=65, chunks=(64,))
+
+
 def test_forty_chunks():
     check_prefix(case_of(63, 64, 2504, seed=11), 2504, (7, 130), seed=2504, chunks=(64, 0))
 

@@ -14,7 +14,7 @@ from cubecobrarecommender_amd.complete import plan_passes
 from cubecobrarecommender_amd.layout import Layout
 from cubecobrarecommender_amd.recommender import Recommender, pack_cubes
 from oracle import model_ref
-from tests import complete_ref
+from tests import complete_ref, tile_cases
 
 pytestmark = pytest.mark.gpu
 
@@ -122,6 +122,19 @@ def test_equals_the_cpu_oracle(per_step):
         want = complete_ref.complete_loop(oracle, cube, size, per_step)
         assert len(want[0]) == 12
         check(g, want)
+
+
+@pytest.mark.parametrize('V,d,R', tile_cases.TILE_CASES)
+def test_equals_the_cpu_oracle_at_the_tile_shapes(V, d, R):
+    """The output tile's edges (tests/tile_cases.py) under the completion entry: every cube grows by
+    4 cards in two passes of one launch of R rows."""
+    rec, cubes = tile_cases.recommender(V, d), tile_cases.cubes(V, R)
+    sizes = [len(c) + 4 for c in cubes]
+    got = rec.complete_many(cubes, sizes, per_step=2)
+    oracle = complete_ref.oracle_recommend(tile_cases.params(V, d), V)
+    assert len(got) == R
+    for cube, size, g in zip(cubes, sizes, got):
+        check(g, complete_ref.complete_loop(oracle, cube, size, 2))
 
 
 # ------------------------------------------------------------------------------ 3. insertion ends

@@ -148,9 +148,14 @@ def test_against_the_oracle(N, kind):
 
 
 @pytest.mark.parametrize('kind', ['relu', 'signed'])
-@pytest.mark.parametrize('K', [5, 32, 33, 70])
+@pytest.mark.parametrize('K', [5, 32, 33, 70, 192])
 def test_other_embedding_widths(K, kind):
     check_case(Case(kind, 300, K, seed=K), (1, 7, 65, 130), seed=K)
+
+
+def test_query_tile_edges():
+    """One query more than a tile of 32 and of 128 (65 is above); 65 cubes: a second cube tile of one."""
+    check_case(Case('dups', 65, 64, seed=65), (33, 129), seed=65)
 
 
 def test_duplicates_in_different_chunks():

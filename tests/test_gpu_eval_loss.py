@@ -15,6 +15,7 @@ from cubecobrarecommender_amd.layout import Layout
 from cubecobrarecommender_amd.model import CC_Recommender
 from cubecobrarecommender_amd.recommender import Recommender, pack_cubes
 from tests import eval_loss_ref as E
+from tests import tile_cases
 from tests.gpu_helpers import problem
 
 pytestmark = pytest.mark.gpu
@@ -94,6 +95,22 @@ def test_direct_call(V, d, kind):
         assert rc == 0
         assert same_bits(loss, ref[0][rows]), (R, loss, ref[0][rows])
         assert np.array_equal(pred, ref[1][rows]), R
+
+
+_tile_refs = {}
+
+
+@pytest.mark.parametrize('V,d,R', tile_cases.TILE_CASES)
+def test_direct_call_tile_shapes(V, d, R):
+    """The loss tile's edges (tests/tile_cases.py); every row's targets are its cube."""
+    rec, cubes = tile_cases.recommender(V, d), tile_cases.cubes(V, R)
+    if (V, d) not in _tile_refs:
+        _tile_refs[(V, d)] = E.reference(tile_cases.params(V, d), tile_cases.cubes(V, tile_cases.MAX_ROWS))
+    ref = _tile_refs[(V, d)]
+    rc, loss, pred, _ = _direct(rec, cubes, cubes)
+    assert rc == 0
+    assert same_bits(loss, ref[0][:R])
+    assert np.array_equal(pred, ref[1][:R])
 
 
 @pytest.mark.parametrize('kind', KINDS)

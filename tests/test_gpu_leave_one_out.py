@@ -10,7 +10,7 @@ from cubecobrarecommender_amd.layout import Layout
 from cubecobrarecommender_amd.leaveoneout import Plan
 from cubecobrarecommender_amd.recommender import Recommender
 from oracle import infer_ref, model_ref
-from tests import loo_ref
+from tests import loo_ref, tile_cases
 
 pytestmark = pytest.mark.gpu
 
@@ -100,6 +100,24 @@ def test_targets_every_card():
             if len(u) else np.zeros((0, V), np.float32)
         assert same(outs[r]['without'], rows[np.searchsorted(u, cube)]), r
         assert same(outs[r]['base'], many[r]['probs']), r
+
+
+def test_tile_shapes():
+    """d = 192 (three chunks of k), T = V = 299 targets (five target tiles, the last of 43 cards: no
+    multiple of 4) and 61 derived rows, of which the second cube's, 21..54, straddle the first row
+    tile; both modes."""
+    V, d = 299, 192
+    P, rec = tile_cases.params(V, d), tile_cases.recommender(V, d)
+    rng = np.random.default_rng(V + d)
+    cubes = [rng.choice(V, n, replace=False) for n in (20, 33, 5)]
+    outs = rec.leave_one_out(cubes, targets=np.arange(V))
+    for r, cube in enumerate(cubes):
+        base, rows = loo_ref.loo_targets(P, cube, np.arange(V))
+        assert same(outs[r]['base'], base) and same(outs[r]['without'], rows), r
+    outs = rec.leave_one_out(cubes)
+    for r, cube in enumerate(cubes):
+        loo, cut = loo_ref.loo_self(P, cube)
+        assert same(outs[r]['loo_vals'], loo) and same(outs[r]['cut_vals'], cut), r
 
 
 def test_targets_short_lists():

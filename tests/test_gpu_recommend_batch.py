@@ -8,6 +8,7 @@ from cubecobrarecommender_amd import _lib as L
 from cubecobrarecommender_amd.layout import Layout
 from cubecobrarecommender_amd.recommender import Recommender, pack_cubes
 from oracle import infer_ref, model_ref
+from tests import tile_cases
 
 pytestmark = pytest.mark.gpu
 
@@ -131,6 +132,16 @@ def test_row_tile_edges():
             check_row(a[r], want[r], cubes[r], 40, probs=True)
             for key in ('additions', 'add_vals', 'cut_vals', 'probs'):
                 assert np.array_equal(a[r][key], b[r][key]), (R, r, key)
+
+
+@pytest.mark.parametrize('V,d,R', tile_cases.TILE_CASES)
+def test_tile_shapes(V, d, R):
+    """The output tile's edges (tests/tile_cases.py), one launch of R rows."""
+    rec, cubes, want = tile_cases.recommender(V, d), tile_cases.cubes(V, R), tile_cases.probs(V, d, R)
+    outs = rec.recommend_many(cubes, 40, want_probs=True)
+    assert len(outs) == R
+    for r in range(R):
+        check_row(outs[r], want[r], cubes[r], 40, probs=True)
 
 
 def test_ties_at_the_threshold():

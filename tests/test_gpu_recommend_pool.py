@@ -11,6 +11,7 @@ from cubecobrarecommender_amd import _lib as L
 from cubecobrarecommender_amd.layout import Layout
 from cubecobrarecommender_amd.recommender import CardPool, Recommender, pack_cubes
 from oracle import infer_ref, model_ref
+from tests import tile_cases
 
 pytestmark = pytest.mark.gpu
 
@@ -155,6 +156,20 @@ def test_pools_bit_exact(V, d, rows):
         assert len(outs[CUBE_ROW + 1]['additions']) == 1           # n = V - 1 and no pool: one candidate
         if V >= 1001:
             assert len(outs[CUBE_ROW - 1]['additions']) > 0
+
+
+@pytest.mark.parametrize('V,d,R', tile_cases.TILE_CASES)
+def test_pools_tile_shapes(V, d, R):
+    """The pooled output tile's edges (tests/tile_cases.py): every other card allowed."""
+    rec, cubes, want = tile_cases.recommender(V, d), tile_cases.cubes(V, R), tile_cases.probs(V, d, R)
+    allowed = np.arange(V) % 2 == 0
+    outs = rec.recommend_many(cubes, 7, want_probs=True, pool=rec.card_pool(np.flatnonzero(allowed)))
+    assert len(outs) == R
+    for r, cube in enumerate(cubes):
+        ok = allowed.copy()
+        ok[cube] = False
+        o = infer_ref.rank(want[r])
+        check_row(outs[r], want[r], cube, o[ok[o]], 7, probs=True)
 
 
 @pytest.mark.parametrize('V,d', SHAPES)

@@ -14,6 +14,7 @@ from cubecobrarecommender_amd.layout import Layout
 from cubecobrarecommender_amd.recommender import Recommender, pack_cubes
 from oracle import infer_ref, model_ref
 from oracle.detmath import det_sigmoid32
+from tests import tile_cases
 
 pytestmark = pytest.mark.gpu
 
@@ -118,6 +119,23 @@ def test_direct_call(V, d):
             lo, hi = row_ptr[r], row_ptr[r + 1]
             assert np.array_equal(cutv[lo:hi], want[r][idx[lo:hi]])
         assert nadd[7] == 0                                 # n = V: no candidate
+
+
+@pytest.mark.parametrize('V,d,R', tile_cases.TILE_CASES)
+def test_direct_call_tile_shapes(V, d, R):
+    """The output tile's edges (tests/tile_cases.py) under the ranking entry."""
+    rec, cubes, want = tile_cases.recommender(V, d), tile_cases.cubes(V, R), tile_cases.probs(V, d, R)
+    rc, row_ptr, idx, nadd, adds, addv, cutv, probs = _direct(rec, cubes, V, want_probs=True)
+    assert rc == 0
+    for r, cube in enumerate(cubes):
+        exp, _ = infer_ref.top_n(want[r], cube, V)
+        k = len(exp)
+        assert nadd[r] == k == V - len(cube)
+        assert np.array_equal(probs[r], want[r])
+        assert np.array_equal(adds[r, :k], exp) and np.array_equal(addv[r, :k], want[r][exp])
+        assert np.all(adds[r, k:] == -1) and np.all(addv[r, k:] == 0.0)
+        lo, hi = row_ptr[r], row_ptr[r + 1]
+        assert np.array_equal(cutv[lo:hi], want[r][idx[lo:hi]])
 
 
 @pytest.mark.parametrize('V,d', SHAPES)

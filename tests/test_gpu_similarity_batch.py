@@ -168,7 +168,7 @@ def test_direct_calls_against_the_oracle_and_the_single_path(V, kind):
 
 
 @pytest.mark.parametrize('kind', ['relu', 'signed'])
-@pytest.mark.parametrize('K', [5, 32, 33, 70])
+@pytest.mark.parametrize('K', [5, 32, 33, 70, 192])
 def test_direct_calls_other_embedding_widths(K, kind):
     check_case(Case(kind, 300, K, seed=K), (1, 7, 65, 130), seed=K)
 
