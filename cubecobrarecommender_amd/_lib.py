@@ -180,6 +180,11 @@ SIGNATURES = {
     'cc_cube_neighbours_max_k': (_I32, []),
     'cc_cube_neighbours_ws_size': (_SZ, [_I32, _I32, _I32, _I32, _I32]),
     'cc_cube_neighbours': (C.c_int, [_P, _I32, _I32, _I32, _I32, _P, _P, _P, _I32, _I32, _P, _P, _P, _P]),
+    'cc_cube_cluster_block': (_I32, []),
+    'cc_cube_cluster_max_k': (_I32, []),
+    'cc_cube_cluster_ws_size': (_SZ, [_I32, _I32, _I32, _I32]),
+    'cc_cube_cluster': (C.c_int, [_P, _I32, _I32, _I32, _I32, _P, _I32, _P, _P, _P, _P, _P, _P, _P, _P]),
+    'cc_cube_assign': (C.c_int, [_P, _I32, _I32, _I32, _I32, _P, _I32, _P, _P, _P, _P, _P, _P]),
     'cc_audience_corpus_size': (_SZ, [_I32, _I32, _I32]),
     'cc_audience_put_ws_size': (_SZ, [_I32, _I32, _I32]),
     'cc_audience_put': (C.c_int, [_P, _I32, _I32, _P, _I32, _I32, _I32, _I32, _I32, _P, _P, _I32, _I32, _P, _P]),

@@ -98,6 +98,45 @@ def similar_cubes(index, cube_indices, k, cube_names=None):
             for i, (j, dv) in enumerate(zip(idx[0], dists[0]))]
 
 
+def cube_clusters_report(clusters, cube_names=None, cubes=None, int_to_card=None, top=10, representatives=5):
+    """The host report of a cubecluster.CubeClusters: per cluster a dict of id, size and
+    representatives [(cube, similarity)], the up to `representatives` members nearest the centroid
+    (cube is the index's cube id, or cube_names[id]; similarity is the cosine, -dist).  With cubes
+    (the index's cubes as card-id lists, in id order) also cards [(card, share, lift)]: the up to
+    `top` cards held by the largest share of the cluster's cubes (equal shares lower card id
+    first; card is the id, or int_to_card[id]), lift their share over the corpus's."""
+    N = clusters.N
+    name = (lambda j: int(j)) if cube_names is None else (lambda j: cube_names[int(j)])
+    card = (lambda c: int(c)) if int_to_card is None else (lambda c: int_to_card[int(c)])
+    if cubes is not None:
+        lists = [np.unique(np.asarray(c, np.int64).reshape(-1)) for c in cubes][:N]
+        V = max([int(l.max()) + 1 for l in lists if len(l)], default=0)
+        corpus = np.zeros(V, np.int64)
+        for l in lists:
+            corpus[l] += 1
+    out = []
+    for c in range(clusters.k):
+        reps = clusters.representatives(c, representatives)
+        row = dict(id=c, size=int(clusters.sizes[c]),
+                   representatives=[(name(j), float(-clusters.dists[j])) for j in reps])
+        if cubes is not None:
+            held = np.zeros(V, np.int64)
+            members = clusters.members(c)
+            for j in members:
+                held[lists[int(j)]] += 1
+            order = np.argsort(-held, kind='stable')[:max(0, int(top))]
+            row['cards'] = [(card(i), held[i] / len(members), (held[i] / len(members)) / (corpus[i] / N))
+                            for i in order if held[i] > 0]
+        out.append(row)
+    return out
+
+
+def cube_clusters(index, k, cube_names=None, cubes=None, int_to_card=None, top=10, representatives=5, **kw):
+    """"What kinds of cube are there" over a cubesim.CubeIndex: index.cluster(k, **kw) (init, seed,
+    max_iter, n_init) and its cube_clusters_report."""
+    return cube_clusters_report(index.cluster(k, **kw), cube_names, cubes, int_to_card, top, representatives)
+
+
 def card_audience(corpus, card_names, k, card_to_int, cube_names=None, include_members=False):
     """"Which cubes want this card" against an audience.CubeCorpus (model.cube_corpus(cubes)): per
     card name of card_names a list of (cube, prob), the up to k cubes with the highest

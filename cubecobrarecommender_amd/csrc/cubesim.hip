@@ -36,6 +36,7 @@
 
 #include "common.hpp"
 #include "cosine.hpp"
+#include "cubeindex.hpp"
 #include "detmath.hpp"
 #include "dottile.hpp"
 #include "rowselect.hpp"
@@ -45,8 +46,11 @@ namespace {
 
 constexpr int TC = dottile::TC;   // cubes per distance tile
 constexpr int DNT = dottile::NT;  // distance-tile workgroup
-constexpr int QNT = 64;       // query rows: one thread each
-constexpr int MAX_Q = 1 << 22;
+using cubeindex::index_layout;
+using cubeindex::IndexLayout;
+using cubeindex::MAX_Q;
+using cubeindex::QNT;
+using cubeindex::query_rows_kernel;  // (cubeindex.hpp, shared with cubecluster.hip)
 
 using detm::addf;
 using detm::mulf;
@@ -62,38 +66,6 @@ using rowsel::write_row;
 using cosine::dist_of_key;
 using cosine::inv_norm;
 using cosine::k_pad;
-
-// Query r (one workgroup each): the index row qid[r] (0 <= qid[r] < N), else the raw embedding
-// zq[r] (a negative or absent id, zq given), else none.
-__global__ __launch_bounds__(QNT) void query_rows_kernel(const float *__restrict__ n, int N, int K, int Kp,
-                                                         const int32_t *__restrict__ qid,
-                                                         const float *__restrict__ zq,
-                                                         float *__restrict__ qn, int32_t *__restrict__ qok) {
-  __shared__ float stage[QNT];
-  __shared__ float s_inv;
-  const int r = blockIdx.x, tid = threadIdx.x;
-  const int id = qid ? qid[r] : -1;  // (block-uniform, as is every branch below)
-  float *out = qn + (int64_t)r * Kp;
-  if ((uint32_t)id < (uint32_t)N) {
-    const float *src = n + (int64_t)id * Kp;
-    for (int i = tid; i < Kp; i += QNT) out[i] = src[i];
-  } else if (id < 0 && zq) {
-    const float *e = zq + (int64_t)r * K;
-    float ss = 0.f;  // thread 0's: the pinned order is sequential
-    for (int k0 = 0; k0 < K; k0 += QNT) {
-      __syncthreads();  // the previous stage is summed
-      if (k0 + tid < K) stage[tid] = e[k0 + tid];
-      __syncthreads();
-      if (tid == 0)
-        for (int c = 0; c < min(QNT, K - k0); ++c) ss = addf(ss, mulf(stage[c], stage[c]));
-    }
-    if (tid == 0) s_inv = inv_norm(ss);
-    __syncthreads();
-    const float inv = s_inv;
-    for (int i = tid; i < Kp; i += QNT) out[i] = i < K ? mulf(e[i], inv) : 0.f;
-  }
-  if (tid == 0) qok[r] = ((uint32_t)id < (uint32_t)N || (id < 0 && zq)) ? 1 : 0;
-}
 
 // keys [Q][pitch] of the chunk's cubes [c0, c0 + cl): key (r, j) = orderable(-dot(qn[r], n[c0 + j]))
 // (4 waves per SIMD, as simbatch.hip's tile has at RM = 8: at most 128 VGPRs)
@@ -203,24 +175,6 @@ CUBESIM_SELECT_KERNEL void merge_rows_kernel(const uint64_t *__restrict__ cand, 
   // chunks * k stays below 2^31: larger counts are refused by the entry
   if (want > 0) select_smallest(s, CandItem{cand + (int64_t)r * chunks * k}, chunks * k, want, (uint32_t)(N - 1));
   write_row(s, want, k, oi, od, dist_of_key);
-}
-
-int cap_pitch(int cap) { return (int)cdiv(std::max(cap, 1), 64) * 64; }
-
-// index: [n cap*Kp][nT Kp*caps]
-struct IndexLayout {
-  size_t n, nT, total;
-  int Kp, caps;
-};
-IndexLayout index_layout(int cap, int K) {
-  IndexLayout x;
-  x.Kp = k_pad(K);
-  x.caps = cap_pitch(cap);
-  size_t o = 0;
-  x.n = o, o += align256((size_t)std::max(cap, 1) * x.Kp * sizeof(float));
-  x.nT = o, o += align256((size_t)x.Kp * x.caps * sizeof(float));
-  x.total = o;
-  return x;
 }
 
 // workspace: [keys Q*pitch][cand Q*chunks*k][qn Q*Kp][qok Q], pitch = the chunk, or N rounded up to

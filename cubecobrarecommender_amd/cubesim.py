@@ -184,3 +184,16 @@ class CubeIndex:
     def table(self, k, rows_per_launch=512, chunk=0):
         """neighbours(range(N), k): every cube's nearest cubes."""
         return self.neighbours(np.arange(self.N, dtype=np.int64), k, rows_per_launch=rows_per_launch, chunk=chunk)
+
+    # ------------------------------------------------------------------ grouping
+    def cluster(self, k, init=None, seed=0, max_iter=50, n_init=1):
+        """The cubes [0, N) in k archetypes: deterministic spherical k-means, all
+        iterations on the device -> cubecluster.CubeClusters.  init: k member ids to start from
+        (duplicates allowed); without it restart r draws
+        np.random.default_rng(seed + r).choice(N, k, replace=False), and of n_init restarts the one
+        with the highest objective is kept, the lower r of equal ones.  The result's every bit is
+        fixed by the index, k, the initial ids and max_iter.  k outside 1..min(N,
+        cc_cube_cluster_max_k()), a negative max_iter, n_init below 1 or a bad init raise ValueError
+        before anything is launched."""
+        from . import cubecluster
+        return cubecluster.cluster(self, k, init=init, seed=seed, max_iter=max_iter, n_init=n_init)

@@ -725,6 +725,49 @@ int cc_cube_neighbours(const void *index, int32_t cap, int32_t N, int32_t K, int
                        int32_t chunk, void *ws, int32_t *out_idx, float *out_dist, void *stream);
 
 /* ----------------------------------------------------------------------------------
+ * Cube archetypes: deterministic spherical k-means (cosine distance, unit centroids) over the
+ * member cubes [0, N) of a cube index (above), and the nearest centroid of member or fresh cubes.
+ * Every output bit is fixed by the index rows, k, the initial ids and max_iter.
+ * PINNED ARITHMETIC: fp32, multiply and add separately rounded, sums from +0.
+ *   assign: dist(i, j) = -(sum_t n_i[t] * c_j[t]) in ascending t, n_i the index row, c_j the
+ *     centroid row as it is (never re-normalised); label[i] is the j of the smallest composite
+ *     (orderable(dist) << 32 | j): equal distances go to the lower centroid; dist[i] is that
+ *     distance, a zero is -0.0f.
+ *   update: with B = cc_cube_cluster_block(), P[b][j][t] = sum of n_i[t] over the cubes i of id
+ *     block [b B, (b + 1) B) with label[i] == j, in ascending i; S[j][t] = sum of P[b][j][t] in
+ *     ascending b; a cluster with members gets S[j] normalised by the put's arithmetic (ss in index
+ *     order, inv = 1 / sqrt(max(ss, 1e-12)), S[j][t] * inv), one without keeps its centroid's bits.
+ *   cc_cube_cluster: C_0 = the index rows init_ids[0..k) (device; duplicates allowed; an id outside
+ *     [0, N) is the caller's to refuse, the device clamps it), L_-1 = all -1.  For t = 0 ..
+ *     max_iter - 1: L_t = assign(C_t), changed[t] = #{L_t != L_t-1}; changed[t] == 0 stops with
+ *     n_iter = t (converged), else C_t+1 = update(L_t).  Without convergence one more assign with
+ *     C_max_iter runs, its count goes to changed[max_iter], and n_iter = max_iter.  label / dist [N]
+ *     are thus the assign of the returned centroids [k][K]; sizes [k] their member counts; changed
+ *     [max_iter + 1] holds -1 behind n_iter.  All iterations are queued on the stream at once; the
+ *     kernels behind a converged assign return at their first instruction.  1 <= k <=
+ *     min(N, cc_cube_cluster_max_k()), max_iter >= 0.  N == 0 returns CC_OK and launches nothing.
+ *   cc_cube_assign: query r as in cc_cube_neighbours (qid, zq); label / dist [Q]: the assign of the
+ *     query's row against centroids [k][K] (device, any rows, as they are); a row that is no query
+ *     gives -1 / 0.f.  Q == 0 returns CC_OK and launches nothing.
+ *   ws: cc_cube_cluster_ws_size(N, K, k, Q) bytes, 256-byte aligned, serves cc_cube_cluster at
+ *     (N, K, k) and cc_cube_assign at (K, k, up to Q rows); an assign alone needs
+ *     cc_cube_cluster_ws_size(0, K, k, Q).  With Kp = K rounded up to 32: the centroid image
+ *     Kp * (k rounded up to 64) floats, the block partials ceil(N / B) * B * Kp floats, their 16-bit
+ *     slot map ceil(N / B) * k, 8 bytes per row of max(N, Q), the query rows Q * (Kp + 1) words; no
+ *     N * k matrix of any kind.
+ *     Nothing in it survives a call.  Only rows [0, N) of the index are read.
+ * ---------------------------------------------------------------------------------- */
+int32_t cc_cube_cluster_block(void);
+int32_t cc_cube_cluster_max_k(void);
+size_t cc_cube_cluster_ws_size(int32_t N, int32_t K, int32_t k, int32_t Q);
+int cc_cube_cluster(const void *index, int32_t cap, int32_t N, int32_t K, int32_t k,
+                    const int32_t *init_ids, int32_t max_iter, void *ws, int32_t *label, float *dist,
+                    float *centroids, int32_t *sizes, int32_t *changed, int32_t *n_iter, void *stream);
+int cc_cube_assign(const void *index, int32_t cap, int32_t N, int32_t K, int32_t k,
+                   const float *centroids, int32_t Q, const int32_t *qid, const float *zq, void *ws,
+                   int32_t *label, float *dist, void *stream);
+
+/* ----------------------------------------------------------------------------------
  * Card audience: a resident corpus of N cubes (ids are positions) and, for T query cards, the k
  * cubes that want each card most.  p[t][c] = det_sigmoid32(blocked_dot(h3[c], Wo[:, t]) + bo[t])
  * with h3[c] the forward pass of cube c: the bits of cc_recommend_batch_fp32's probs[c][t] and of
