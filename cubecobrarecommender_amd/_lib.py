@@ -248,6 +248,12 @@ SIGNATURES = {
     'cc_complete_ws_size': (_SZ, [_I32, _I32, _I32, _I32, _I32]),
     'cc_complete_fp32': (C.c_int, [_P, _I32, _I32, _I32, _P, _P, _I32, _P, _I32, _I32, _P, _I32, _P, _I32, _P, _P,
                                    _P, _P, _SZ, _P]),
+    'cc_recommend_diverse_max_candidates': (_I32, []),
+    'cc_recommend_diverse_ws_size': (_SZ, [_I32, _I32, _I32, _I32, _I32, _I32]),
+    # params, V, d, R, row_ptr, idx, max_n, amount, M, lambda, emb, K, pools, n_pools, pool_of_row, A,
+    # n_add, additions, add_vals, redundancy, base_rank, cut_vals, ws, ws_bytes, stream
+    'cc_recommend_diverse_fp32': (C.c_int, [_P, _I32, _I32, _I32, _P, _P, _I32, _I32, _I32, _F32, _P, _I32, _P,
+                                            _I32, _P, _I32, _P, _P, _P, _P, _P, _P, _P, _SZ, _P]),
     'cc_adjacency_ws_size':(_SZ, [_I32, _I32, _I32, _I32]),
     'cc_adjacency': (C.c_int, [_P, _P, _I32, _I32, _I32, _P, _P, _P, _P, _P, _P]),
     'cc_graph_rec_max_amount': (_I32, []),

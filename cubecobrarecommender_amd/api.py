@@ -178,6 +178,19 @@ def complete_cube(model, cube_indices, size, int_to_card, pool=None, per_step=1)
     return {'additions': {int_to_card[idx]: p for idx, p in zip(out['added'].tolist(), out['added_vals'].tolist())}}
 
 
+def recommend_diverse(model, cube_indices, amount, int_to_card, trade=0.7, candidates=None, pool=None):
+    """`amount` recommendations for one cube, re-ranked for diversity (Recommender.recommend_diverse):
+    {"additions": {name: p}, "redundancy": {name: cosine to the nearest card picked before it},
+    "base_rank": {name: 0-based position in the plain ranking}}, all in the order picked.
+    trade=1 is the plain ranking; pool: a CardPool the cards come from."""
+    out = model.recommender().recommend_diverse(list(cube_indices), amount, trade=trade, candidates=candidates,
+                                                pool=pool)
+    names = [int_to_card[idx] for idx in out['additions'].tolist()]
+    return {'additions': dict(zip(names, out['add_vals'].tolist())),
+            'redundancy': dict(zip(names, out['redundancy'].tolist())),
+            'base_rank': dict(zip(names, out['base_rank'].tolist()))}
+
+
 def explain(model, cube_indices, target_ids, int_to_card, top=10):
     """Why was a card recommended?  {target name: {"base": p(t | cube), "cards": [(name, gain)]}}
     with gain = p(t | cube) - p(t | cube without c) (a float32 subtraction) for the `top` distinct

@@ -567,6 +567,35 @@ class Recommender:
         """`complete_many` for one cube: {'added', 'added_vals'}."""
         return self.complete_many([cube_indices], size, per_step=per_step, pool=pool)[0]
 
+    # ------------------------------------------------------------------ diverse recommendations
+    def recommend_diverse_many(self, cubes, amount, trade=0.7, candidates=None, pool=None, emb=None,
+                               rows_per_launch=512):
+        """`recommend_many` re-ranked for diversity on the device (cc_recommend_diverse_fp32):
+        greedy maximal marginal relevance over every cube's first `candidates` additions.  With
+        c, p the additions and add_vals of recommend_many(cube, candidates, pool=pool), lam =
+        np.float32(trade), mu = 1 - lam and red[j] = 0, pick number t is the untaken position j
+        with the greatest (lam * p[j]) - (mu * red[j]) (fp32, every operation rounded; equal scores:
+        the smaller j); then red[j] = max(red[j], sim(c[j], c[pick])) for every untaken j, sim the
+        cosine of the cards' rows of `emb`, bit for bit the negated distance of similar_many.
+        min(max(amount, 1), len(c)) cards are picked.  trade=1 is recommend_many(cubes, amount).
+
+        candidates: None means min(cc_recommend_diverse_max_candidates(), max(4 * amount, 64)).
+        emb: a [V, K] float32 table (tensor or array); None means similarity.card_embeddings.
+        pool: as for recommend_many.
+        Returns a list of dicts: additions int32, add_vals float32 (the bits of recommend_many),
+        redundancy float32 (red[pick] when picked), base_rank int32 (the position j), all in pick
+        order, and cut_vals as recommend_many returns them.  A trade outside [0, 1], candidates
+        outside [1, cc_recommend_diverse_max_candidates()], a table that is not [V, K] or too wide
+        for that many candidates, an id outside [0, V) and a wrong pool raise ValueError before
+        anything is launched."""
+        from .diverse import recommend_diverse_many
+        return recommend_diverse_many(self, cubes, amount, trade, candidates, pool, emb, rows_per_launch)
+
+    def recommend_diverse(self, cube_indices, amount, trade=0.7, candidates=None, pool=None, emb=None):
+        """`recommend_diverse_many` for one cube."""
+        return self.recommend_diverse_many([cube_indices], amount, trade=trade, candidates=candidates, pool=pool,
+                                           emb=emb)[0]
+
     def _full_order(self, probs, uniq, amount):
         """The complete ranking (cc_topn with `order`; tests and tools only)."""
         V, dev = self.V, self.dev

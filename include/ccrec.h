@@ -1040,6 +1040,54 @@ int cc_complete_fp32(const float *params, int32_t V, int32_t d, int32_t R, const
                      const int32_t *pool_of_row, int32_t A, int32_t *n_added, int32_t *added,
                      float *added_vals, void *ws, size_t ws_bytes, void *stream);
 
+/* Diverse recommendations: greedy maximal marginal relevance (MMR) over every row's first M
+ * candidates, one stream of launches, no host round trip.  Row r is defined by
+ *   c[0..cnt), p[0..cnt): the additions and add_vals of cc_recommend_batch_fp32 (or of
+ *   cc_recommend_batch_pool_fp32, with pools) on the row at amount = M; cnt <= M.
+ *   sim(a, b), PINNED, fp32, multiply and add separately rounded, sums in index order from +0:
+ *     ss = sum_i e_i * e_i;  inv = 1 / sqrtf(fmaxf(ss, 1e-12f));  n_i = e_i * inv
+ *     sim(a, b) = sum_i n_a,i * n_b,i      (e: a row of emb; bit for bit the negated distance of
+ *                                           cc_similar_cards, and symmetric)
+ *   mu = 1 - lambda (one fp32 subtraction);  red[j] = +0.0f for every position j
+ *   for t in [0, picks), picks = min(max(amount, 1), cnt):
+ *     score[j] = (lambda * p[j]) - (mu * red[j])        two multiplies and one subtraction, each
+ *                                                        rounded, never contracted
+ *     pick = the untaken j of greatest score (compared as numbers), equal scores: smallest j
+ *     emit c[pick], p[pick], red[pick], pick;  pick is taken
+ *     for every untaken j: s = sim(c[j], c[pick]);  if (s > red[j]) red[j] = s
+ * and every id and value is bit for bit that loop's.  lambda == 1 returns the first picks entries
+ * of cc_recommend_batch_fp32 at any M >= amount; so does an all-zero emb at any lambda.
+ *   row_ptr [R + 1], idx, max_n: the cubes' CSR with the PRECONDITIONS of cc_recommend_batch_fp32;
+ *   neither is written.
+ *   M in [1, cc_recommend_diverse_max_candidates()] (512); emb [V][K] fp32 (device), K >= 1: the
+ *   candidates' normalised rows are held in LDS, k-major, K padded to a multiple of 32 (Kp), so
+ *   Kp * (M | 1) must not exceed 64 * (cc_recommend_diverse_max_candidates() | 1): K <= 64 allows
+ *   every M, a wider table fewer candidates.
+ *   pools, n_pools, pool_of_row: as for cc_recommend_batch_pool_fp32; all three NULL / 0 / NULL is
+ *   the unpooled call.
+ *   n_add [R] = picks; additions / add_vals / redundancy / base_rank [R][A]: the picks in the order
+ *   taken: card id, p, the redundancy charged (red[pick] when picked), the 0-based position in the
+ *   candidate list.  Entries at and past n_add[r] are NOT written.  A >= min(max(amount, 1), M).
+ *   cut_vals [row_ptr[R]]: as cc_recommend_batch_fp32 writes them.
+ *   ws: ws_bytes >= cc_recommend_diverse_ws_size(V, d, R, max_n, M, K) bytes, 256-B aligned: the
+ *   pooled select workspace and R * (2 M + 1) words of candidates; the call does not depend on its
+ *   contents.  R == 0 returns CC_OK without a launch (and writes nothing).  A row's bits do not
+ *   depend on R or on what else is in the batch.
+ * CC_ERR_ARG: null pointer, max_n > V, d not a multiple of 64 in [64, 1024], K < 1, lambda outside
+ * [0, 1] or NaN, M or Kp * (M | 1) out of range, A below min(max(amount, 1), M), pool_of_row null
+ * with pools given, n_pools < 0, pools null with n_pools > 0, unaligned or undersized ws; nothing
+ * is launched or written. */
+int32_t cc_recommend_diverse_max_candidates(void);
+size_t cc_recommend_diverse_ws_size(int32_t V, int32_t d, int32_t R, int32_t max_n, int32_t M,
+                                    int32_t K);
+int cc_recommend_diverse_fp32(const float *params, int32_t V, int32_t d, int32_t R,
+                              const int32_t *row_ptr, const int32_t *idx, int32_t max_n,
+                              int32_t amount, int32_t M, float lambda, const float *emb, int32_t K,
+                              const uint32_t *pools, int32_t n_pools, const int32_t *pool_of_row,
+                              int32_t A, int32_t *n_add, int32_t *additions, float *add_vals,
+                              float *redundancy, int32_t *base_rank, float *cut_vals, void *ws,
+                              size_t ws_bytes, void *stream);
+
 /* ---------------------------------------------------------------- card co-occurrence graph (N1)
  * Replaces src/non_ml/utils.py:75-91 (create_adjacency_matrix, called by
  * src/non_ml/create_mtx.py:19) and the M~ normalisation of src/ml/train.py:69-71.
