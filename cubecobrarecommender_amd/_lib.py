@@ -104,6 +104,23 @@ def _w1_grad_args(adam, reg, riders):
     return _W1 + out + (_W1_ADAM if adam else []) + tail + (_W1_DW if riders else []) + [_P]   # ..., stream
 
 
+# The six batched recommend entries (csrc/recbatch.hip): select, full ranking and target ranks, each
+# with a card-pool twin that takes pools, n_pools, pool_of_row before the stream.
+_BATCH = [_P, _I32, _I32, _I32, _P, _P, _I32]                 # params, V, d, R, row_ptr, idx, max_n
+_BATCH_ADD = _BATCH + [_I32, _P, _P, _P, _P, _P, _P]          # amount, ws, n_add, additions, add_vals, cut_vals, probs
+# tgt_ptr, tgt, cutoffs, n_cutoffs, ws, ranks, tgt_vals, hits, cut_vals, probs
+_BATCH_TGT = _BATCH + [_P, _P, _P, _I32, _P, _P, _P, _P, _P, _P]
+_POOL = [_P, _I32, _P]
+
+
+def _batch_entries():
+    forms = [(kind + pool, args + tail + [_P]) for kind, args in (('', _BATCH_ADD), ('_rank', _BATCH_ADD),
+                                                                  ('_target_ranks', _BATCH_TGT))
+             for pool, tail in (('', []), ('_pool', _POOL))]
+    return {f'cc_recommend_batch{form}{end}': sig for form, args in forms
+            for end, sig in (('_ws_size', (_SZ, [_I32] * 4)), ('_fp32', (C.c_int, args)))}
+
+
 # name -> (restype, argtypes); every symbol include/ccrec.h declares
 SIGNATURES = {
     'cc_abi_version': (C.c_int, []),
@@ -221,24 +238,7 @@ SIGNATURES = {
     'cc_recommend_graph_run': (C.c_int, [_P, _P, _I32]),
     'cc_recommend_graph_destroy': (C.c_int, [_P]),
     'cc_recommend_batch_max_amount': (_I32, []),
-    'cc_recommend_batch_ws_size': (_SZ, [_I32, _I32, _I32, _I32]),
-    'cc_recommend_batch_fp32': (C.c_int, [_P, _I32, _I32, _I32, _P, _P, _I32, _I32, _P, _P, _P, _P, _P, _P, _P]),
-    'cc_recommend_batch_rank_ws_size': (_SZ, [_I32, _I32, _I32, _I32]),
-    'cc_recommend_batch_rank_fp32': (C.c_int, [_P, _I32, _I32, _I32, _P, _P, _I32, _I32, _P, _P, _P, _P, _P, _P,
-                                               _P]),
-    'cc_recommend_batch_target_ranks_ws_size': (_SZ, [_I32, _I32, _I32, _I32]),
-    'cc_recommend_batch_target_ranks_fp32': (C.c_int, [_P, _I32, _I32, _I32, _P, _P, _I32, _P, _P, _P, _I32, _P,
-                                                       _P, _P, _P, _P, _P, _P]),
-    # card pools: the unpooled entry's arguments, then pools, n_pools, pool_of_row before the stream
-    'cc_recommend_batch_pool_ws_size': (_SZ, [_I32, _I32, _I32, _I32]),
-    'cc_recommend_batch_pool_fp32': (C.c_int, [_P, _I32, _I32, _I32, _P, _P, _I32, _I32, _P, _P, _P, _P, _P, _P,
-                                               _P, _I32, _P, _P]),
-    'cc_recommend_batch_rank_pool_ws_size': (_SZ, [_I32, _I32, _I32, _I32]),
-    'cc_recommend_batch_rank_pool_fp32': (C.c_int, [_P, _I32, _I32, _I32, _P, _P, _I32, _I32, _P, _P, _P, _P, _P,
-                                                    _P, _P, _I32, _P, _P]),
-    'cc_recommend_batch_target_ranks_pool_ws_size': (_SZ, [_I32, _I32, _I32, _I32]),
-    'cc_recommend_batch_target_ranks_pool_fp32': (C.c_int, [_P, _I32, _I32, _I32, _P, _P, _I32, _P, _P, _P, _I32,
-                                                            _P, _P, _P, _P, _P, _P, _P, _I32, _P, _P]),
+    **_batch_entries(),
     'cc_recommend_batch_loss_ws_size': (_SZ, [_I32, _I32, _I32, _I32]),
     'cc_recommend_batch_loss_fp32': (C.c_int, [_P, _I32, _I32, _I32, _P, _P, _I32, _P, _P, _P, _P, _P, _P]),
     'cc_leave_one_out_ws_size': (_SZ, [_I32, _I32, _I32, _I32, _I32]),

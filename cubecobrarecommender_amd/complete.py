@@ -66,10 +66,8 @@ def complete_many(rec, cubes, sizes, per_step=1, pool=None, rows_per_launch=512)
         rp_d, ix_d, tn_d = upload(row_ptr, dev), upload(idx, dev), upload(target, dev)
         ints = torch.empty(Rc * (1 + A), device=dev, dtype=torch.int32)      # n_added, added
         vals = torch.empty(Rc * A, device=dev, dtype=torch.float32)
-        pool_args = (None, 0, None)
-        if pools is not None:
-            por_d = upload(pool_of_row[r0:r1], dev)
-            pool_args = (L.ptr(table), len(pools), L.ptr(por_d))
+        por_d = upload(pool_of_row[r0:r1], dev) if pools is not None else None
+        pool_args = rec._pool_args(table, por_d, none=(None, 0, None))
         L.call('cc_complete_fp32', L.ptr(rec.params), V, d, Rc, L.ptr(rp_d), L.ptr(ix_d), max_n, L.ptr(tn_d),
                per_step, passes, *pool_args, A, L.ptr(ints), L.ptr(ints[Rc:]), L.ptr(vals), L.ptr(ws),
                ws.numel() * 4, L.stream_ptr(rec.stream))

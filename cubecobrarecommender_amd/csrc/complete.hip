@@ -142,11 +142,7 @@ extern "C" int cc_complete_fp32(const float *params, int32_t V, int32_t d, int32
                                 void *ws, size_t ws_bytes, void *stream) {
   CC_REQUIRE(params && row_ptr && idx && target_n && n_added && added && added_vals && ws,
              "cc_complete_fp32: null pointer");
-  if (pools || n_pools || pool_of_row) {  // a pooled call: the pooled entries' own rules
-    CC_REQUIRE(pool_of_row, "cc_complete_fp32: null pointer (pool_of_row with pools)");
-    CC_REQUIRE(n_pools >= 0, "cc_complete_fp32: n_pools is negative");
-    CC_REQUIRE(pools || n_pools == 0, "cc_complete_fp32: pools is null with n_pools > 0");
-  }
+  if (int rc = cc::pools_check("cc_complete_fp32", pools, n_pools, pool_of_row, true)) return rc;
   CC_REQUIRE(V > 0 && R >= 0 && max_n >= 0 && max_n <= V && A >= 1,
              "cc_complete_fp32: V/R/max_n/A");
   if (int rc = cc::infer_check_d(d, "cc_complete_fp32")) return rc;

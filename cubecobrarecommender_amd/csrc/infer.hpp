@@ -19,6 +19,8 @@ int infer_towers_launch(const float *params, int V, int d, int R, const int32_t 
 // recbatch.hip
 int row_bits_launch(const int32_t *row_ptr, const int32_t *idx, int R, int V, int VW, uint32_t *bits,
                     hipStream_t s);
+int pools_check(const char *who, const uint32_t *pools, int n_pools, const int32_t *pool_of_row,
+                bool optional);
 int batch_max_amount();
 size_t batch_select_ws_bytes(int V, int d, int R, int max_n, bool pooled);
 int batch_select_launch(const float *params, int V, int d, int R, const int32_t *row_ptr,

@@ -33,7 +33,9 @@
 //                     the cube word; topn_rows_kernel<true> / rank_rows_kernel<true> take want from
 //                     n_cand[r] instead of V - n; target_ranks_kernel is fed the pooled keys.
 // cc::batch_select_launch is the select chain (keys + topn_rows_kernel, pooled or not) as
-// complete.hip runs it pass after pass; the two select entries are that call behind their checks.
+// complete.hip runs it pass after pass; the two select entries run its pieces behind their checks.
+// Host half: six entries = a null-pointer check + batch_front (every other check, the keys) + one
+// of three back halves (select_launch, rank_launch, the target_ranks_kernel launch).
 #include "common.hpp"
 #include "detmath.hpp"
 #include "dottile.hpp"
@@ -594,10 +596,6 @@ void launch_out(dim3 grid, hipStream_t s, const float *h3, const float *Wo, cons
 
 extern "C" int32_t cc_recommend_batch_max_amount(void) { return MAX_AMOUNT; }
 
-extern "C" size_t cc_recommend_batch_ws_size(int32_t V, int32_t d, int32_t R, int32_t max_n) {
-  return batch_ws(V, d, R, max_n).total + 256;
-}
-
 int cc::row_bits_launch(const int32_t *row_ptr, const int32_t *idx, int R, int V, int VW,
                         uint32_t *bits, hipStream_t s) {
   hipLaunchKernelGGL(row_bits_kernel, dim3(R), dim3(256), 0, s, row_ptr, idx, V, VW, bits);
@@ -605,52 +603,125 @@ int cc::row_bits_launch(const int32_t *row_ptr, const int32_t *idx, int R, int V
   return CC_OK;
 }
 
+// A pooled call's argument checks (who: the entry's name).  optional: the entry takes pools or none
+// (complete.hip, diverse.hip), so the rules hold once any of the three is given.
+int cc::pools_check(const char *who, const uint32_t *pools, int n_pools, const int32_t *pool_of_row,
+                    bool optional) {
+  if (optional && !(pools || n_pools || pool_of_row)) return CC_OK;
+  const std::string w(who);
+  CC_REQUIRE(pool_of_row, w + (optional ? ": null pointer (pool_of_row with pools)" : ": null pointer"));
+  CC_REQUIRE(n_pools >= 0, w + ": n_pools is negative");
+  CC_REQUIRE(pools || n_pools == 0, w + ": pools is null with n_pools > 0");
+  return CC_OK;
+}
+
+namespace {
+// The arguments all six entries share.
+struct BatchArgs {
+  const float *params;
+  int V, d, R;
+  const int32_t *row_ptr, *idx;
+  int max_n;
+  void *ws;
+  float *cut_vals, *probs;
+  hipStream_t s;
+};
+
+// What the front leaves for a back half: the layout, the rows' keys, a pooled call's candidate
+// counts (null without pools) and the bytes of workspace the chain (with the pools' share) holds.
+struct BatchKeys {
+  BatchWs w;
+  const uint32_t *keys;
+  const int32_t *n_cand;
+  size_t after;
+};
+}  // namespace
+
 // The launches all entries share: row masks, h3, then the output layer, which leaves every row's
 // sort keys in the workspace, its cut values and (on request) its probabilities.  pl: a pooled
-// call's arguments, or null; *n_cand then points at the rows' candidate counts, or is null.
-static int batch_keys_launch(const float *params, int V, int d, int R, const int32_t *row_ptr,
-                             const int32_t *idx, int max_n, void *ws, const BatchWs &w,
-                             float *cut_vals, float *probs, hipStream_t s,
-                             const Pools *pl = nullptr, const int32_t **n_cand = nullptr) {
+// call's arguments, or null.  The arguments are checked; R > 0.
+static int batch_keys_launch(const BatchArgs &a, const Pools *pl, BatchKeys *k) {
   int64_t off[CC_NUM_TENSORS], sz[CC_NUM_TENSORS], tot, mt;
-  if (int rc = cc::param_offsets(V, d, off, sz, &tot, &mt)) return rc;
-  char *base = (char *)ws;
+  if (int rc = cc::param_offsets(a.V, a.d, off, sz, &tot, &mt)) return rc;
+  const BatchWs w = batch_ws(a.V, a.d, a.R, a.max_n);
+  char *base = (char *)a.ws;
   float *h3 = (float *)(base + w.h3);
   uint32_t *keys = (uint32_t *)(base + w.keys), *bits = (uint32_t *)(base + w.bits);
   const uint32_t *excl = nullptr;
+  *k = BatchKeys{w, keys, nullptr, w.total};
   if (pl) {
-    const PoolWs p = pool_ws(w, R);
+    const PoolWs p = pool_ws(w, a.R);
     excl = (const uint32_t *)(base + p.excl);
-    *n_cand = (const int32_t *)(base + p.ncand);
-    hipLaunchKernelGGL(row_mask_kernel, dim3(R), dim3(256), 0, s, row_ptr, idx, V, w.VW, pl->pools,
-                       pl->n_pools, pl->pool_of_row, bits, (uint32_t *)(base + p.excl),
+    k->n_cand = (const int32_t *)(base + p.ncand);
+    k->after = p.total;
+    hipLaunchKernelGGL(row_mask_kernel, dim3(a.R), dim3(256), 0, a.s, a.row_ptr, a.idx, a.V, w.VW,
+                       pl->pools, pl->n_pools, pl->pool_of_row, bits, (uint32_t *)(base + p.excl),
                        (int32_t *)(base + p.ncand));
     CC_LAUNCH_CHECK("row_mask_kernel");
-  } else if (int rc = cc::row_bits_launch(row_ptr, idx, R, V, w.VW, bits, s)) {
+  } else if (int rc = cc::row_bits_launch(a.row_ptr, a.idx, a.R, a.V, w.VW, bits, a.s)) {
     return rc;
   }
-  if (int rc = cc::infer_h3_launch(params, V, d, R, row_ptr, idx, max_n, (float *)(base + w.part),
-                                   (float *)(base + w.zlat), h3, s))
+  if (int rc = cc::infer_h3_launch(a.params, a.V, a.d, a.R, a.row_ptr, a.idx, a.max_n,
+                                   (float *)(base + w.part), (float *)(base + w.zlat), h3, a.s))
     return rc;
-  const float *Wo = params + off[14], *bo = params + off[15];
-  const dim3 grid((unsigned)cdiv(V, TC), 1);
+  const float *Wo = a.params + off[14], *bo = a.params + off[15];
+  const dim3 grid((unsigned)cdiv(a.V, TC), 1);
   // rows per tile: 32 / 64 / 128 (the arithmetic per (row, card) does not depend on it)
-  if (R <= 32)
-    launch_out<2>(grid, s, h3, Wo, bo, d, V, R, row_ptr, idx, bits, w.VW, keys, w.Vs, cut_vals, probs, excl);
-  else if (R <= 64)
-    launch_out<4>(grid, s, h3, Wo, bo, d, V, R, row_ptr, idx, bits, w.VW, keys, w.Vs, cut_vals, probs, excl);
-  else
-    launch_out<8>(grid, s, h3, Wo, bo, d, V, R, row_ptr, idx, bits, w.VW, keys, w.Vs, cut_vals, probs, excl);
+  const auto out = a.R <= 32 ? &launch_out<2> : a.R <= 64 ? &launch_out<4> : &launch_out<8>;
+  out(grid, a.s, h3, Wo, bo, a.d, a.V, a.R, a.row_ptr, a.idx, bits, w.VW, keys, w.Vs, a.cut_vals,
+      a.probs, excl);
   CC_LAUNCH_CHECK("out_tile_kernel");
   return CC_OK;
 }
 
-// The pooled entries' own argument checks (who: the entry's name).
-static int pools_check(const std::string &who, const uint32_t *pools, int n_pools,
-                       const int32_t *pool_of_row) {
-  CC_REQUIRE(pool_of_row, who + ": null pointer");
-  CC_REQUIRE(n_pools >= 0, who + ": n_pools is negative");
-  CC_REQUIRE(pools || n_pools == 0, who + ": pools is null with n_pools > 0");
+// The checked front of all six entries, behind the entry's own null-pointer check (who: the
+// entry's name): the pools' rules for a pooled call, the common rules with the entry's own one
+// (own_ok, own_msg behind the name) where it has always stood, between d and the workspace's
+// alignment, then the keys.  R == 0 is no error and launches nothing (*k is then not written):
+// the entry returns in place of its back half.
+static int batch_front(const char *who, const BatchArgs &a, const Pools *pl, bool own_ok,
+                       const char *own_msg, BatchKeys *k) {
+  const std::string w(who);
+  if (pl)
+    if (int rc = cc::pools_check(who, pl->pools, pl->n_pools, pl->pool_of_row, false)) return rc;
+  CC_REQUIRE(a.V > 0 && a.R >= 0 && a.max_n >= 0 && a.max_n <= a.V, w + ": V/R/max_n");
+  if (int rc = cc::infer_check_d(a.d, who)) return rc;
+  CC_REQUIRE(own_ok, w + own_msg);
+  CC_REQUIRE(((uintptr_t)a.ws & 255) == 0, w + ": ws must be 256-byte aligned");
+  if (a.R == 0) return CC_OK;
+  return batch_keys_launch(a, pl, k);
+}
+
+// The back halves, on the keys of a launched front (the third, target_ranks_kernel, stands in its
+// entry).  The select: every row's first
+// max(amount, 1) candidates; the row pitch of additions / add_vals is max(amount, 1).
+static int select_launch(const BatchArgs &a, const BatchKeys &k, int amount, int32_t *n_add,
+                         int32_t *additions, float *add_vals) {
+  const int A = amount > 0 ? amount : 1;
+  const auto kernel = k.n_cand ? &topn_rows_kernel<true> : &topn_rows_kernel<false>;
+  hipLaunchKernelGGL(kernel, dim3(a.R), dim3(SNT), 0, a.s, k.keys, k.w.Vs, a.V, a.row_ptr, amount,
+                     A, n_add, additions, add_vals, k.n_cand);
+  CC_LAUNCH_CHECK("topn_rows_kernel");
+  return CC_OK;
+}
+
+// rank workspace: the chain's, then the two (key', card) ping-pong buffers [R][Vp] of 64-bit
+// words; Vp is a multiple of 16, so no two rows share a 128-byte line
+static size_t rank_pitch(int V) { return ((size_t)std::max(V, 1) + 15) & ~(size_t)15; }
+static size_t rank_buf_bytes(int V, int R) {
+  return align256((size_t)std::max(R, 1) * rank_pitch(V) * sizeof(uint64_t));
+}
+
+// The full ranking: any amount, result rows of min(max(amount, 1), V) entries.
+static int rank_launch(const BatchArgs &a, const BatchKeys &k, int amount, int32_t *n_add,
+                       int32_t *additions, float *add_vals) {
+  char *bufs = (char *)a.ws + k.after;
+  uint64_t *pa = (uint64_t *)bufs, *pb = (uint64_t *)(bufs + rank_buf_bytes(a.V, a.R));
+  const int A = std::min(amount > 0 ? amount : 1, a.V);
+  const auto kernel = k.n_cand ? &rank_rows_kernel<true> : &rank_rows_kernel<false>;
+  hipLaunchKernelGGL(kernel, dim3(a.R), dim3(SNT), 0, a.s, k.keys, k.w.Vs, a.V, a.row_ptr, amount,
+                     A, pa, pb, (int)rank_pitch(a.V), n_add, additions, add_vals, k.n_cand);
+  CC_LAUNCH_CHECK("rank_rows_kernel");
   return CC_OK;
 }
 
@@ -665,54 +736,61 @@ size_t batch_select_ws_bytes(int V, int d, int R, int max_n, bool pooled) {
 }
 
 // The chain behind cc_recommend_batch_fp32 (pool_of_row null) and cc_recommend_batch_pool_fp32:
-// keys, then the select of every row's first max(amount, 1) candidates; the row pitch of
-// additions / add_vals is max(amount, 1).  The arguments are the entries', already checked; R > 0.
+// keys, then the select.  The arguments are the entries', already checked; R > 0.
 int batch_select_launch(const float *params, int V, int d, int R, const int32_t *row_ptr,
                         const int32_t *idx, int max_n, int amount, void *ws, int32_t *n_add,
                         int32_t *additions, float *add_vals, float *cut_vals, float *probs,
                         const uint32_t *pools, int n_pools, const int32_t *pool_of_row,
                         hipStream_t s) {
-  const BatchWs w = batch_ws(V, d, R, max_n);
-  const uint32_t *keys = (const uint32_t *)((char *)ws + w.keys);
-  const int A = amount > 0 ? amount : 1;
-  if (!pool_of_row) {
-    if (int rc = batch_keys_launch(params, V, d, R, row_ptr, idx, max_n, ws, w, cut_vals, probs, s))
-      return rc;
-    hipLaunchKernelGGL(topn_rows_kernel<false>, dim3(R), dim3(SNT), 0, s, keys, w.Vs, V, row_ptr,
-                       amount, A, n_add, additions, add_vals, (const int32_t *)nullptr);
-  } else {
-    const Pools pl{pools, n_pools, pool_of_row};
-    const int32_t *n_cand = nullptr;
-    if (int rc = batch_keys_launch(params, V, d, R, row_ptr, idx, max_n, ws, w, cut_vals, probs, s,
-                                   &pl, &n_cand))
-      return rc;
-    hipLaunchKernelGGL(topn_rows_kernel<true>, dim3(R), dim3(SNT), 0, s, keys, w.Vs, V, row_ptr,
-                       amount, A, n_add, additions, add_vals, n_cand);
-  }
-  CC_LAUNCH_CHECK("topn_rows_kernel");
-  return CC_OK;
+  const BatchArgs a{params, V, d, R, row_ptr, idx, max_n, ws, cut_vals, probs, s};
+  const Pools pl{pools, n_pools, pool_of_row};
+  BatchKeys k;
+  if (int rc = batch_keys_launch(a, pool_of_row ? &pl : nullptr, &k)) return rc;
+  return select_launch(a, k, amount, n_add, additions, add_vals);
 }
 }  // namespace cc
+
+// ------------------------------------------------------------------------------------ the entries
+// Workspace of an entry: the chain's (pooled: with the pools' share), the ranking's two buffers,
+// and 256 bytes for the caller to align in.
+static size_t entry_ws_size(int V, int d, int R, int max_n, bool pooled, bool ranked) {
+  return cc::batch_select_ws_bytes(V, d, R, max_n, pooled) + (ranked ? 2 * rank_buf_bytes(V, R) : 0) +
+         256;
+}
+#define CC_BATCH_WS_SIZE(name, pooled, ranked)                             \
+  extern "C" size_t name(int32_t V, int32_t d, int32_t R, int32_t max_n) { \
+    return entry_ws_size(V, d, R, max_n, pooled, ranked);                  \
+  }
+CC_BATCH_WS_SIZE(cc_recommend_batch_ws_size, false, false)
+CC_BATCH_WS_SIZE(cc_recommend_batch_pool_ws_size, true, false)
+CC_BATCH_WS_SIZE(cc_recommend_batch_rank_ws_size, false, true)
+CC_BATCH_WS_SIZE(cc_recommend_batch_rank_pool_ws_size, true, true)
+CC_BATCH_WS_SIZE(cc_recommend_batch_target_ranks_ws_size, false, false)
+CC_BATCH_WS_SIZE(cc_recommend_batch_target_ranks_pool_ws_size, true, false)
+#undef CC_BATCH_WS_SIZE
+
+// cc_recommend_batch[_rank][_pool]_fp32 (who); rank: the full ranking, which has no amount cap.
+static int recommend_entry(const char *who, bool rank, const BatchArgs &a, int amount,
+                           int32_t *n_add, int32_t *additions, float *add_vals, const Pools *pl) {
+  CC_REQUIRE(a.params && a.row_ptr && a.idx && a.ws && n_add && additions && add_vals && a.cut_vals,
+             std::string(who) + ": null pointer");
+  BatchKeys k;
+  if (int rc = batch_front(who, a, pl, rank || amount <= MAX_AMOUNT,
+                           ": amount above cc_recommend_batch_max_amount()", &k))
+    return rc;
+  if (a.R == 0) return CC_OK;
+  return (rank ? rank_launch : select_launch)(a, k, amount, n_add, additions, add_vals);
+}
 
 extern "C" int cc_recommend_batch_fp32(const float *params, int32_t V, int32_t d, int32_t R,
                                        const int32_t *row_ptr, const int32_t *idx, int32_t max_n,
                                        int32_t amount, void *ws, int32_t *n_add,
                                        int32_t *additions, float *add_vals, float *cut_vals,
                                        float *probs, void *stream) {
-  CC_REQUIRE(params && row_ptr && idx && ws && n_add && additions && add_vals && cut_vals,
-             "cc_recommend_batch_fp32: null pointer");
-  CC_REQUIRE(V > 0 && R >= 0 && max_n >= 0 && max_n <= V, "cc_recommend_batch_fp32: V/R/max_n");
-  if (int rc = cc::infer_check_d(d, "cc_recommend_batch_fp32")) return rc;
-  CC_REQUIRE(amount <= MAX_AMOUNT,
-             "cc_recommend_batch_fp32: amount above cc_recommend_batch_max_amount()");
-  CC_REQUIRE(((uintptr_t)ws & 255) == 0, "cc_recommend_batch_fp32: ws must be 256-byte aligned");
-  if (R == 0) return CC_OK;
-  return cc::batch_select_launch(params, V, d, R, row_ptr, idx, max_n, amount, ws, n_add, additions,
-                                 add_vals, cut_vals, probs, nullptr, 0, nullptr, as_stream(stream));
-}
-
-extern "C" size_t cc_recommend_batch_pool_ws_size(int32_t V, int32_t d, int32_t R, int32_t max_n) {
-  return pool_ws(batch_ws(V, d, R, max_n), R).total + 256;
+  return recommend_entry(
+      "cc_recommend_batch_fp32", false,
+      {params, V, d, R, row_ptr, idx, max_n, ws, cut_vals, probs, as_stream(stream)}, amount, n_add,
+      additions, add_vals, nullptr);
 }
 
 extern "C" int cc_recommend_batch_pool_fp32(const float *params, int32_t V, int32_t d, int32_t R,
@@ -722,31 +800,11 @@ extern "C" int cc_recommend_batch_pool_fp32(const float *params, int32_t V, int3
                                             float *cut_vals, float *probs, const uint32_t *pools,
                                             int32_t n_pools, const int32_t *pool_of_row,
                                             void *stream) {
-  CC_REQUIRE(params && row_ptr && idx && ws && n_add && additions && add_vals && cut_vals,
-             "cc_recommend_batch_pool_fp32: null pointer");
-  if (int rc = pools_check("cc_recommend_batch_pool_fp32", pools, n_pools, pool_of_row)) return rc;
-  CC_REQUIRE(V > 0 && R >= 0 && max_n >= 0 && max_n <= V,
-             "cc_recommend_batch_pool_fp32: V/R/max_n");
-  if (int rc = cc::infer_check_d(d, "cc_recommend_batch_pool_fp32")) return rc;
-  CC_REQUIRE(amount <= MAX_AMOUNT,
-             "cc_recommend_batch_pool_fp32: amount above cc_recommend_batch_max_amount()");
-  CC_REQUIRE(((uintptr_t)ws & 255) == 0,
-             "cc_recommend_batch_pool_fp32: ws must be 256-byte aligned");
-  if (R == 0) return CC_OK;
-  return cc::batch_select_launch(params, V, d, R, row_ptr, idx, max_n, amount, ws, n_add, additions,
-                                 add_vals, cut_vals, probs, pools, n_pools, pool_of_row,
-                                 as_stream(stream));
-}
-
-// rank workspace: the batch workspace, then the two (key', card) ping-pong buffers [R][Vp] of
-// 64-bit words; Vp is a multiple of 16, so no two rows share a 128-byte line
-static size_t rank_pitch(int V) { return ((size_t)std::max(V, 1) + 15) & ~(size_t)15; }
-static size_t rank_buf_bytes(int V, int R) {
-  return align256((size_t)std::max(R, 1) * rank_pitch(V) * sizeof(uint64_t));
-}
-
-extern "C" size_t cc_recommend_batch_rank_ws_size(int32_t V, int32_t d, int32_t R, int32_t max_n) {
-  return batch_ws(V, d, R, max_n).total + 2 * rank_buf_bytes(V, R) + 256;
+  const Pools pl{pools, n_pools, pool_of_row};
+  return recommend_entry(
+      "cc_recommend_batch_pool_fp32", false,
+      {params, V, d, R, row_ptr, idx, max_n, ws, cut_vals, probs, as_stream(stream)}, amount, n_add,
+      additions, add_vals, &pl);
 }
 
 extern "C" int cc_recommend_batch_rank_fp32(const float *params, int32_t V, int32_t d, int32_t R,
@@ -754,32 +812,10 @@ extern "C" int cc_recommend_batch_rank_fp32(const float *params, int32_t V, int3
                                             int32_t max_n, int32_t amount, void *ws,
                                             int32_t *n_add, int32_t *additions, float *add_vals,
                                             float *cut_vals, float *probs, void *stream) {
-  CC_REQUIRE(params && row_ptr && idx && ws && n_add && additions && add_vals && cut_vals,
-             "cc_recommend_batch_rank_fp32: null pointer");
-  CC_REQUIRE(V > 0 && R >= 0 && max_n >= 0 && max_n <= V,
-             "cc_recommend_batch_rank_fp32: V/R/max_n");
-  if (int rc = cc::infer_check_d(d, "cc_recommend_batch_rank_fp32")) return rc;
-  CC_REQUIRE(((uintptr_t)ws & 255) == 0,
-             "cc_recommend_batch_rank_fp32: ws must be 256-byte aligned");
-  if (R == 0) return CC_OK;
-  const BatchWs w = batch_ws(V, d, R, max_n);
-  hipStream_t s = as_stream(stream);
-  if (int rc = batch_keys_launch(params, V, d, R, row_ptr, idx, max_n, ws, w, cut_vals, probs, s))
-    return rc;
-  char *base = (char *)ws;
-  uint64_t *pa = (uint64_t *)(base + w.total), *pb = (uint64_t *)(base + w.total + rank_buf_bytes(V, R));
-  const int A = std::min(amount > 0 ? amount : 1, V);
-  hipLaunchKernelGGL(rank_rows_kernel<false>, dim3(R), dim3(SNT), 0, s,
-                     (const uint32_t *)(base + w.keys), w.Vs, V, row_ptr, amount, A, pa, pb,
-                     (int)rank_pitch(V), n_add, additions, add_vals, (const int32_t *)nullptr);
-  CC_LAUNCH_CHECK("rank_rows_kernel");
-  return CC_OK;
-}
-
-// pooled rank workspace: the batch workspace, the pool's share, then the ping-pong buffers
-extern "C" size_t cc_recommend_batch_rank_pool_ws_size(int32_t V, int32_t d, int32_t R,
-                                                       int32_t max_n) {
-  return pool_ws(batch_ws(V, d, R, max_n), R).total + 2 * rank_buf_bytes(V, R) + 256;
+  return recommend_entry(
+      "cc_recommend_batch_rank_fp32", true,
+      {params, V, d, R, row_ptr, idx, max_n, ws, cut_vals, probs, as_stream(stream)}, amount, n_add,
+      additions, add_vals, nullptr);
 }
 
 extern "C" int cc_recommend_batch_rank_pool_fp32(
@@ -787,39 +823,34 @@ extern "C" int cc_recommend_batch_rank_pool_fp32(
     const int32_t *idx, int32_t max_n, int32_t amount, void *ws, int32_t *n_add,
     int32_t *additions, float *add_vals, float *cut_vals, float *probs, const uint32_t *pools,
     int32_t n_pools, const int32_t *pool_of_row, void *stream) {
-  CC_REQUIRE(params && row_ptr && idx && ws && n_add && additions && add_vals && cut_vals,
-             "cc_recommend_batch_rank_pool_fp32: null pointer");
-  if (int rc = pools_check("cc_recommend_batch_rank_pool_fp32", pools, n_pools, pool_of_row))
-    return rc;
-  CC_REQUIRE(V > 0 && R >= 0 && max_n >= 0 && max_n <= V,
-             "cc_recommend_batch_rank_pool_fp32: V/R/max_n");
-  if (int rc = cc::infer_check_d(d, "cc_recommend_batch_rank_pool_fp32")) return rc;
-  CC_REQUIRE(((uintptr_t)ws & 255) == 0,
-             "cc_recommend_batch_rank_pool_fp32: ws must be 256-byte aligned");
-  if (R == 0) return CC_OK;
-  const BatchWs w = batch_ws(V, d, R, max_n);
-  hipStream_t s = as_stream(stream);
   const Pools pl{pools, n_pools, pool_of_row};
-  const int32_t *n_cand = nullptr;
-  if (int rc = batch_keys_launch(params, V, d, R, row_ptr, idx, max_n, ws, w, cut_vals, probs, s,
-                                 &pl, &n_cand))
-    return rc;
-  char *base = (char *)ws;
-  const size_t after = pool_ws(w, R).total;
-  uint64_t *pa = (uint64_t *)(base + after), *pb = (uint64_t *)(base + after + rank_buf_bytes(V, R));
-  const int A = std::min(amount > 0 ? amount : 1, V);
-  hipLaunchKernelGGL(rank_rows_kernel<true>, dim3(R), dim3(SNT), 0, s,
-                     (const uint32_t *)(base + w.keys), w.Vs, V, row_ptr, amount, A, pa, pb,
-                     (int)rank_pitch(V), n_add, additions, add_vals, n_cand);
-  CC_LAUNCH_CHECK("rank_rows_kernel");
-  return CC_OK;
+  return recommend_entry(
+      "cc_recommend_batch_rank_pool_fp32", true,
+      {params, V, d, R, row_ptr, idx, max_n, ws, cut_vals, probs, as_stream(stream)}, amount, n_add,
+      additions, add_vals, &pl);
 }
 
-// Ranks of chosen cards: the shared chain leaves the keys in the batch workspace (nothing more is
-// needed: no ping-pong buffers, no R x V result), then one counting workgroup per row.
-extern "C" size_t cc_recommend_batch_target_ranks_ws_size(int32_t V, int32_t d, int32_t R,
-                                                          int32_t max_n) {
-  return batch_ws(V, d, R, max_n).total + 256;
+// cc_recommend_batch_target_ranks[_pool]_fp32 (who).  Ranks of chosen cards: one counting workgroup
+// per row on the keys (no ping-pong buffers, no R x V result).  The pooled keys give a card outside
+// its row's pool key' = 0, as a cube card has: the kernel ranks such a target -1 with value 0 and
+// counts the pool's candidates alone.
+static int target_ranks_entry(const char *who, const BatchArgs &a, const int32_t *tgt_ptr,
+                              const int32_t *tgt, const int32_t *cutoffs, int n_cutoffs,
+                              int32_t *ranks, float *tgt_vals, unsigned long long *hits,
+                              const Pools *pl) {
+  CC_REQUIRE(a.params && a.row_ptr && a.idx && tgt_ptr && tgt && a.ws && ranks && tgt_vals &&
+                 a.cut_vals,
+             std::string(who) + ": null pointer");
+  BatchKeys k;
+  if (int rc = batch_front(who, a, pl,
+                           n_cutoffs >= 0 && n_cutoffs <= MAX_CUTOFFS && (n_cutoffs == 0 || cutoffs),
+                           ": n_cutoffs outside 0..8, or cutoffs null", &k))
+    return rc;
+  if (a.R == 0) return CC_OK;
+  hipLaunchKernelGGL(target_ranks_kernel, dim3(a.R), dim3(SNT), 0, a.s, k.keys, k.w.Vs, a.V,
+                     tgt_ptr, tgt, cutoffs, n_cutoffs, ranks, tgt_vals, hits);
+  CC_LAUNCH_CHECK("target_ranks_kernel");
+  return CC_OK;
 }
 
 extern "C" int cc_recommend_batch_target_ranks_fp32(
@@ -827,32 +858,10 @@ extern "C" int cc_recommend_batch_target_ranks_fp32(
     const int32_t *idx, int32_t max_n, const int32_t *tgt_ptr, const int32_t *tgt,
     const int32_t *cutoffs, int32_t n_cutoffs, void *ws, int32_t *ranks, float *tgt_vals,
     unsigned long long *hits, float *cut_vals, float *probs, void *stream) {
-  CC_REQUIRE(params && row_ptr && idx && tgt_ptr && tgt && ws && ranks && tgt_vals && cut_vals,
-             "cc_recommend_batch_target_ranks_fp32: null pointer");
-  CC_REQUIRE(V > 0 && R >= 0 && max_n >= 0 && max_n <= V,
-             "cc_recommend_batch_target_ranks_fp32: V/R/max_n");
-  if (int rc = cc::infer_check_d(d, "cc_recommend_batch_target_ranks_fp32")) return rc;
-  CC_REQUIRE(n_cutoffs >= 0 && n_cutoffs <= MAX_CUTOFFS && (n_cutoffs == 0 || cutoffs),
-             "cc_recommend_batch_target_ranks_fp32: n_cutoffs outside 0..8, or cutoffs null");
-  CC_REQUIRE(((uintptr_t)ws & 255) == 0,
-             "cc_recommend_batch_target_ranks_fp32: ws must be 256-byte aligned");
-  if (R == 0) return CC_OK;
-  const BatchWs w = batch_ws(V, d, R, max_n);
-  hipStream_t s = as_stream(stream);
-  if (int rc = batch_keys_launch(params, V, d, R, row_ptr, idx, max_n, ws, w, cut_vals, probs, s))
-    return rc;
-  hipLaunchKernelGGL(target_ranks_kernel, dim3(R), dim3(SNT), 0, s,
-                     (const uint32_t *)((char *)ws + w.keys), w.Vs, V, tgt_ptr, tgt, cutoffs,
-                     n_cutoffs, ranks, tgt_vals, hits);
-  CC_LAUNCH_CHECK("target_ranks_kernel");
-  return CC_OK;
-}
-
-// The pooled keys give a card outside its row's pool key' = 0, as a cube card has: the counting
-// kernel ranks such a target -1 with value 0 and counts the pool's candidates alone.
-extern "C" size_t cc_recommend_batch_target_ranks_pool_ws_size(int32_t V, int32_t d, int32_t R,
-                                                               int32_t max_n) {
-  return pool_ws(batch_ws(V, d, R, max_n), R).total + 256;
+  return target_ranks_entry(
+      "cc_recommend_batch_target_ranks_fp32",
+      {params, V, d, R, row_ptr, idx, max_n, ws, cut_vals, probs, as_stream(stream)}, tgt_ptr, tgt,
+      cutoffs, n_cutoffs, ranks, tgt_vals, hits, nullptr);
 }
 
 extern "C" int cc_recommend_batch_target_ranks_pool_fp32(
@@ -861,29 +870,9 @@ extern "C" int cc_recommend_batch_target_ranks_pool_fp32(
     const int32_t *cutoffs, int32_t n_cutoffs, void *ws, int32_t *ranks, float *tgt_vals,
     unsigned long long *hits, float *cut_vals, float *probs, const uint32_t *pools,
     int32_t n_pools, const int32_t *pool_of_row, void *stream) {
-  CC_REQUIRE(params && row_ptr && idx && tgt_ptr && tgt && ws && ranks && tgt_vals && cut_vals,
-             "cc_recommend_batch_target_ranks_pool_fp32: null pointer");
-  if (int rc = pools_check("cc_recommend_batch_target_ranks_pool_fp32", pools, n_pools,
-                           pool_of_row))
-    return rc;
-  CC_REQUIRE(V > 0 && R >= 0 && max_n >= 0 && max_n <= V,
-             "cc_recommend_batch_target_ranks_pool_fp32: V/R/max_n");
-  if (int rc = cc::infer_check_d(d, "cc_recommend_batch_target_ranks_pool_fp32")) return rc;
-  CC_REQUIRE(n_cutoffs >= 0 && n_cutoffs <= MAX_CUTOFFS && (n_cutoffs == 0 || cutoffs),
-             "cc_recommend_batch_target_ranks_pool_fp32: n_cutoffs outside 0..8, or cutoffs null");
-  CC_REQUIRE(((uintptr_t)ws & 255) == 0,
-             "cc_recommend_batch_target_ranks_pool_fp32: ws must be 256-byte aligned");
-  if (R == 0) return CC_OK;
-  const BatchWs w = batch_ws(V, d, R, max_n);
-  hipStream_t s = as_stream(stream);
   const Pools pl{pools, n_pools, pool_of_row};
-  const int32_t *n_cand = nullptr;
-  if (int rc = batch_keys_launch(params, V, d, R, row_ptr, idx, max_n, ws, w, cut_vals, probs, s,
-                                 &pl, &n_cand))
-    return rc;
-  hipLaunchKernelGGL(target_ranks_kernel, dim3(R), dim3(SNT), 0, s,
-                     (const uint32_t *)((char *)ws + w.keys), w.Vs, V, tgt_ptr, tgt, cutoffs,
-                     n_cutoffs, ranks, tgt_vals, hits);
-  CC_LAUNCH_CHECK("target_ranks_kernel");
-  return CC_OK;
+  return target_ranks_entry(
+      "cc_recommend_batch_target_ranks_pool_fp32",
+      {params, V, d, R, row_ptr, idx, max_n, ws, cut_vals, probs, as_stream(stream)}, tgt_ptr, tgt,
+      cutoffs, n_cutoffs, ranks, tgt_vals, hits, &pl);
 }

@@ -84,10 +84,8 @@ def recommend_diverse_many(rec, cubes, amount, trade=DEFAULT_TRADE, candidates=N
         rp_d, ix_d = upload(row_ptr, dev), upload(idx, dev)
         ints = torch.empty(Rc * (1 + 2 * A), device=dev, dtype=torch.int32)      # n_add, additions, base_rank
         flts = torch.empty(2 * Rc * A + max(nnz, 1), device=dev, dtype=torch.float32)   # add_vals, redundancy, cuts
-        pool_args = (None, 0, None)
-        if pools is not None:
-            por_d = upload(pool_of_row[r0:r1], dev)
-            pool_args = (L.ptr(table), len(pools), L.ptr(por_d))
+        por_d = upload(pool_of_row[r0:r1], dev) if pools is not None else None
+        pool_args = rec._pool_args(table, por_d, none=(None, 0, None))
         L.call('cc_recommend_diverse_fp32', L.ptr(rec.params), V, d, Rc, L.ptr(rp_d), L.ptr(ix_d), max_n, amount, M,
                float(lam), L.ptr(emb), K, *pool_args, A, L.ptr(ints), L.ptr(ints[Rc:]), L.ptr(flts),
                L.ptr(flts[Rc * A:]), L.ptr(ints[Rc * (1 + A):]), L.ptr(flts[2 * Rc * A:]), L.ptr(ws),

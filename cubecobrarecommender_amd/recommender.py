@@ -292,6 +292,12 @@ class Recommender:
                 for p in pools]
         return torch.stack(rows).contiguous()
 
+    @staticmethod
+    def _pool_args(table, pool_of_row_dev, none=()):
+        """The pool arguments of an entry call, (pools, n_pools, pool_of_row), from the call's
+        _pool_table and the span's uploaded pool_of_row; `none` without a table (no pools)."""
+        return none if table is None else (L.ptr(table), table.shape[0], L.ptr(pool_of_row_dev))
+
     # ------------------------------------------------------------------ single-cube request
     def recommend(self, cube_indices, amount, want_probs=False, want_order=False, pool=None):
         """ml_recommend.py:78-108 for one cube.  Returns dict with additions (card idx,
@@ -393,13 +399,10 @@ class Recommender:
             ints = torch.empty(Rc * (1 + A), device=dev, dtype=torch.int32)      # n_add, additions
             flts = torch.empty(Rc * A + max(nnz, 1), device=dev, dtype=torch.float32)  # add_vals, cuts
             probs = torch.empty(Rc, V, device=dev, dtype=torch.float32) if want_probs else None
-            pool_args = ()
-            if pools is not None:
-                por_d = upload(pool_of_row[r0:r1], dev)
-                pool_args = (L.ptr(table), len(pools), L.ptr(por_d))
+            por_d = upload(pool_of_row[r0:r1], dev) if pools is not None else None
             L.call(entry, L.ptr(self.params), V, d, Rc, L.ptr(rp_d), L.ptr(ix_d), max_n,
                    amount, L.ptr(ws), L.ptr(ints), L.ptr(ints[Rc:]), L.ptr(flts),
-                   L.ptr(flts[Rc * A:]), L.ptr(probs), *pool_args, L.stream_ptr(self.stream))
+                   L.ptr(flts[Rc * A:]), L.ptr(probs), *self._pool_args(table, por_d), L.stream_ptr(self.stream))
             host = [stage.kept(t, (turn & 1, i)) if rank else stage.fresh(t)
                     for i, t in enumerate((ints, flts, probs) if want_probs else (ints, flts))]
             return (nnz, slot, host), mark(self.stream)
@@ -459,14 +462,11 @@ class Recommender:
         entry, ws_size = stem + '_fp32', getattr(L.lib(), stem + '_ws_size')
 
         def call(s):
-            pool_args = ()
-            if pools is not None:
-                por_d = upload(pool_of_row[s.r0:s.r1], dev)
-                pool_args = (L.ptr(table), len(pools), L.ptr(por_d))
+            por_d = upload(pool_of_row[s.r0:s.r1], dev) if pools is not None else None
             ws = self._batch_ws.get(ws_size(V, d, s.Rc, s.max_n), dev)
             L.call(entry, L.ptr(self.params), V, d, s.Rc, L.ptr(s.rp), L.ptr(s.ix), s.max_n, L.ptr(s.tp),
                    L.ptr(s.tg), L.ptr(s.cut), s.nk, L.ptr(ws), L.ptr(s.rk), L.ptr(s.tv), L.ptr(s.hits),
-                   L.ptr(s.cuts), None, *pool_args, L.stream_ptr(self.stream))
+                   L.ptr(s.cuts), None, *self._pool_args(table, por_d), L.stream_ptr(self.stream))
 
         with self.lock, torch.cuda.stream(self.stream):
             table = self._pool_table(pools) if pools is not None else None
