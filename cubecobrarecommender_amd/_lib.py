@@ -209,6 +209,15 @@ SIGNATURES = {
     'cc_audience_ws_size': (_SZ, [_I32, _I32, _I32, _I32, _I32]),
     'cc_audience_fp32': (C.c_int, [_P, _I32, _I32, _P, _I32, _I32, _I32, _P, _I32, _I32, _I32, _F32, _P, _P, _P, _P,
                                    _P]),
+    'cc_audience_corpus_ptr_offset': (_SZ, [_I32, _I32]),
+    'cc_audience_corpus_ids_offset': (_SZ, [_I32, _I32]),
+    'cc_group_cards_tile': (_I32, []),
+    'cc_group_cards_max_groups': (_I32, []),
+    'cc_group_cards_ws_size': (_SZ, [_I32, _I32, _I32, _I32]),
+    # row_ptr, idx, R, V, label, G, accumulate, path, ws, count, size, total, stream
+    'cc_group_cards_count': (C.c_int, [_P, _P, _I32, _I32, _P, _I32, _I32, _I32, _P, _P, _P, _P, _P]),
+    # count, size, total, V, G, kind, min_count, m, ws, cards, card_count, found, stream
+    'cc_group_cards_top': (C.c_int, [_P, _P, _P, _I32, _I32, _I32, _I32, _I32, _P, _P, _P, _P, _P]),
     'cc_embed_grad_packed': (C.c_int, [_P, _I32, _I32, _I32, _I32, _P, _P, _P, _P]),
     **{w1_grad_name(*form): (C.c_int, _w1_grad_args(*form)) for form in W1_GRAD_FORMS},
     'cc_embed_grad_cs_tickets': (_I32, [_I32, _I32, _I32]),

@@ -137,6 +137,20 @@ def cube_clusters(index, k, cube_names=None, cubes=None, int_to_card=None, top=1
     return cube_clusters_report(index.cluster(k, **kw), cube_names, cubes, int_to_card, top, representatives)
 
 
+def archetype_cards(clusters, cubes_or_corpus, m, int_to_card=None, kind='lift', min_count=1):
+    """"Which cards make this archetype" for a cubecluster.CubeClusters and its cubes (card-id lists
+    in id order, or an audience.CubeCorpus of them): clusters.signature_cards and, per cluster, a
+    dict of id, size and cards [(card, rate, lift)], best first; rate is the share of the cluster's
+    cubes that hold the card, lift that minus the corpus's share.  card is the id, or
+    int_to_card[id]."""
+    res = clusters.signature_cards(cubes_or_corpus, m, kind=kind, min_count=min_count)
+    card = (lambda c: int(c)) if int_to_card is None else (lambda c: int_to_card[int(c)])
+    return [dict(id=g, size=int(res.sizes[g]),
+                 cards=[(card(c), float(res.rate[g, i]), float(res.lift[g, i]))
+                        for i, c in enumerate(res.list_of(g).tolist())])
+            for g in range(res.G)]
+
+
 def card_audience(corpus, card_names, k, card_to_int, cube_names=None, include_members=False):
     """"Which cubes want this card" against an audience.CubeCorpus (model.cube_corpus(cubes)): per
     card name of card_names a list of (cube, prob), the up to k cubes with the highest

@@ -145,6 +145,15 @@ class CubeCorpus:
             del last                  # only now (launches.pipelined)
         return self._result(out_i, out_p, counts, n)
 
+    def group_cards(self, labels, m, kind='lift', min_count=1, G=None, counts=False, rows_per_launch=1 << 20):
+        """The corpus's cubes grouped by labels (one per cube, -1: ignored) -> groupcards.GroupCards
+        (DESIGN §4.13), the integers groupcards.group_cards gives for the same cubes, counted from
+        the resident card lists: no card is uploaded.  len(labels) must equal len(corpus);
+        rows_per_launch: corpus cubes per launch (the result does not depend on it)."""
+        from . import groupcards
+        return groupcards.corpus_group_cards(self, labels, m, kind=kind, min_count=min_count, G=G, counts=counts,
+                                             rows_per_launch=rows_per_launch)
+
     @staticmethod
     def _result(out_i, out_p, counts, n):
         members, candidates, above = (np.ascontiguousarray(counts[:, j]) for j in range(3))

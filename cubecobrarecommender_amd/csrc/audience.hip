@@ -401,6 +401,10 @@ extern "C" size_t cc_audience_corpus_size(int32_t cap, int32_t card_cap, int32_t
   return corpus_layout(cap, d).ids + align256((size_t)std::max(card_cap, 1) * sizeof(int32_t));
 }
 
+extern "C" size_t cc_audience_corpus_ptr_offset(int32_t cap, int32_t d) { return corpus_layout(cap, d).ptr; }
+
+extern "C" size_t cc_audience_corpus_ids_offset(int32_t cap, int32_t d) { return corpus_layout(cap, d).ids; }
+
 extern "C" size_t cc_audience_put_ws_size(int32_t R, int32_t d, int32_t max_n) {
   return put_ws(R, d, max_n).total;
 }

@@ -121,6 +121,22 @@ class CubeClusters:
         ids = self.members(c)
         return ids[np.argsort(self.dists[ids], kind='stable')[:max(0, int(m))]]
 
+    def signature_cards(self, cubes_or_corpus, m, kind='lift', min_count=1):
+        """What every archetype plays: groupcards.GroupCards of the clustered cubes
+        under `labels`, m cards per cluster.  cubes_or_corpus: the N cubes of the clustering as
+        card-id lists in id order, or an audience.CubeCorpus holding exactly them; any other count
+        raises ValueError."""
+        from . import groupcards
+        if len(cubes_or_corpus) != self.N:
+            raise ValueError(f'{len(cubes_or_corpus)} cubes for a clustering of {self.N}')
+        if hasattr(cubes_or_corpus, 'group_cards'):
+            return cubes_or_corpus.group_cards(self.labels, m, kind=kind, min_count=min_count, G=self.k)
+        V = self.index.V      # an index of given latents knows no cards: the cubes' own range then
+        if not V:
+            V = max([int(np.max(c)) + 1 for c in cubes_or_corpus if len(c)], default=1)
+        return groupcards.group_cards(cubes_or_corpus, self.labels, V, m, kind=kind, min_count=min_count, G=self.k,
+                                      device=self.index.dev)
+
     def _cluster(self, c):
         c = int(c)
         if not 0 <= c < self.k:

@@ -809,6 +809,58 @@ int cc_audience_fp32(const float *params, int32_t V, int32_t d, const void *corp
                      int32_t N, int32_t T, const int32_t *cards, int32_t k, int32_t chunk,
                      int32_t include_members, float threshold, void *ws, int32_t *out_idx,
                      float *out_p, int32_t *out_counts, void *stream);
+/* The byte offsets of ptr [cap + 1] and ids [card_cap] within a corpus (they do not depend on
+ * card_cap): cube c's sorted distinct cards are ids[ptr[c] .. ptr[c + 1]), the CSR that
+ * cc_group_cards_count takes. */
+size_t cc_audience_corpus_ptr_offset(int32_t cap, int32_t d);
+size_t cc_audience_corpus_ids_offset(int32_t cap, int32_t d);
+
+/* ----------------------------------------------------------------------------------
+ * Archetype card profiles: a group-by of cubes by an integer label into card counts per group, and
+ * per group the m cards with the largest rank key.  ALL INTEGERS: every output bit is fixed by the
+ * definition, whatever the path, the spans a corpus is streamed in or the run.
+ *   Cubes: the CSR of R cubes (row_ptr [R + 1] int32, cube r's ids idx[row_ptr[r] .. row_ptr[r + 1]),
+ *     sorted and distinct, in [0, V); row_ptr[0] may be any offset into idx).  label [R] in [-1, G):
+ *     a cube labelled -1 is ignored.  (The device uses neither a label outside [0, G) nor an id
+ *     outside [0, V) as an index.)
+ *   count[g][v] (uint32 [G][V]) = the cubes of label g that hold card v; size[g] (int32 [G]) = the
+ *     cubes of label g; total[v] (uint32 [V]) = sum over g of count[g][v]; N = sum over g of size[g].
+ *   cc_group_cards_count: accumulate == 0 zeroes count, size and total first; accumulate == 1 adds
+ *     the R cubes to what an earlier call left in the three arrays (a corpus streams through in
+ *     spans; integer adds commute: the same bits whatever the spans).  R == 0 launches nothing
+ *     beyond the zeroing.  path: 1 the LDS-privatised histograms (cubes grouped by label on the
+ *     device, a workgroup per slice of a group and tile of cc_group_cards_tile() cards; total is then
+ *     recomputed as the column sums of count), 2 one global integer atomic per id into count and
+ *     into total, 0 chosen by shape (2 where R < 2 G: hardly a cube per group).
+ *   cc_group_cards_top: with a = count[g][v], t = total[v], s = size[g], the key k of card v in
+ *     group g is   CC_GROUP_RATE: a    CC_GROUP_LIFT: a N - t s    CC_GROUP_AVOID: t s - a N
+ *     (lift orders as a / s - t / N and as the in-group minus the out-of-group rate, whose
+ *     difference is k / (s (N - s)): s and N are constant within a group).  A card is a candidate
+ *     of g when a >= max(min_count, 1) (AVOID: t >= max(min_count, 1)); the group's list is its
+ *     candidates by k descending, equal k lower card first.  found[g] = min(m, candidates), 0 for
+ *     a group of size 0; cards [G][m] the list's first found[g] cards then -1; card_count [G][m]
+ *     their a, then 0.  N is derived from size on the device.  Nothing is floating point: a caller
+ *     derives rate = a / s, base = t / N, lift = rate - base from the integers.
+ *   LIMITS: 1 <= V <= 2^18, 1 <= G <= cc_group_cards_max_groups() (at least 1024), 0 <= R <= 2^22 per
+ *     call, 1 <= m <= 1024, min_count >= 0, and N <= 2^22 (a larger N gives found 0 everywhere), so
+ *     that |k| <= 2^44 and (2^45 - k) << 18 | v is a unique 64-bit composite whose ascending order
+ *     is the list's.  Counts are 32 bits.
+ *   ws: cc_group_cards_ws_size(R, V, G, m) bytes, 256-byte aligned, serves both entries: the cube
+ *     ids grouped by label (4 R), the label counts, starts and cursors (12 G) and the slice list
+ *     (8 (G + R / 256)); no histogram and no second [G][V] table.  Nothing in it survives a call.
+ *   CC_ERR_ARG, nothing launched: null or unaligned pointer, a limit above, accumulate outside 0..1,
+ *     path outside 0..2, kind none of the three.
+ * ---------------------------------------------------------------------------------- */
+enum { CC_GROUP_RATE = 0, CC_GROUP_LIFT = 1, CC_GROUP_AVOID = 2 };
+int32_t cc_group_cards_tile(void);
+int32_t cc_group_cards_max_groups(void);
+size_t cc_group_cards_ws_size(int32_t R, int32_t V, int32_t G, int32_t m);
+int cc_group_cards_count(const int32_t *row_ptr, const int32_t *idx, int32_t R, int32_t V,
+                         const int32_t *label, int32_t G, int32_t accumulate, int32_t path, void *ws,
+                         uint32_t *count, int32_t *size, uint32_t *total, void *stream);
+int cc_group_cards_top(const uint32_t *count, const int32_t *size, const uint32_t *total, int32_t V,
+                       int32_t G, int32_t kind, int32_t min_count, int32_t m, void *ws, int32_t *cards,
+                       uint32_t *card_count, int32_t *found, void *stream);
 
 /* ----------------------------------------------------------------------------------
  * Top-N (ml_recommend.py:87-108): rank all V probabilities descending, ties -> higher
