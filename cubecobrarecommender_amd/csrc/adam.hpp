@@ -3,23 +3,14 @@
 //   alpha = lr sqrt(1-b2^t)/(1-b1^t); m += (g-m)(1-b1); v += (g^2-v)(1-b2);
 //   p -= m*alpha/(sqrt(v)+eps);  t = state[0] + 1.
 #pragma once
-// build knob (A/B builds): the dense Adam's p / m / v / g streams non-temporal (1) or default (0);
-// measured (r05zm): default policy 149.7 -> 164.8-167.2 us/step (BCE), 961 -> 1,020 (config 5)
-#ifndef ADAM_NT
-#define ADAM_NT 1
-#endif
+// the dense Adam's p / m / v / g streams are non-temporal; measured (r05zm): the default policy
+// 149.7 -> 164.8-167.2 us/step (BCE), 961 -> 1,020 (config 5)
 #include "common.hpp"
 
 template <typename T>
-__device__ __forceinline__ T ADAM_LD(const T *p) {
-  if constexpr (ADAM_NT) return __builtin_nontemporal_load(p);
-  else return *p;
-}
+__device__ __forceinline__ T ADAM_LD(const T *p) { return __builtin_nontemporal_load(p); }
 template <typename T>
-__device__ __forceinline__ void ADAM_ST(T v, T *p) {
-  if constexpr (ADAM_NT) __builtin_nontemporal_store(v, p);
-  else *p = v;
-}
+__device__ __forceinline__ void ADAM_ST(T v, T *p) { __builtin_nontemporal_store(v, p); }
 
 namespace cc_adam {
 

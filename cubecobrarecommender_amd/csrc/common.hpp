@@ -20,13 +20,9 @@ __device__ __forceinline__ int cc_xcd_run(int b, int nb) {
   const int q = nb / 8, r = nb % 8, x = b % 8, slot = b / 8;
   return x < r ? x * (q + 1) + slot : r * (q + 1) + (x - r) * q + slot;
 }
-// CCREC_XCD_SLICES (build knob for the A/B, default on): the fused output-layer kernels (D1's
-// dec_bce_dw, D2's kl_stats / kl_main) take their 96-column slice from cc_xcd_run instead of
-// blockIdx.x
-#ifndef CCREC_XCD_SLICES
-#define CCREC_XCD_SLICES 1
-#endif
-__device__ __forceinline__ int cc_slice_of_block(int b, int nb) { return CCREC_XCD_SLICES ? cc_xcd_run(b, nb) : b; }
+// the fused output-layer kernels (D1's dec_bce_dw, D2's kl_stats / kl_main) take their 96-column
+// slice from cc_xcd_run instead of blockIdx.x
+__device__ __forceinline__ int cc_slice_of_block(int b, int nb) { return cc_xcd_run(b, nb); }
 
 // ------------------------------------------------------------------ error plumbing (host)
 namespace cc {

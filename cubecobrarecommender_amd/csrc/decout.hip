@@ -32,8 +32,8 @@ constexpr float LOG2E = 1.4426950408889634f, LN2 = 0.6931471805599453f;
 // next dX kernel, which reads dZ from L2, 16 -> 19 us; non-temporal dWo neutral)
 constexpr int DEC_CPOL = 0;
 // The two waves of a SIMD run the VALU-bound BCE epilogue together; issue arbitration favours the
-// older one, so waves 4-7 finish ~3.6 us later and the barrier after phase 1 waits for them (probe:
-// tools/micro/dec_probe2.hip).  In pass ps the half (w >> 2) == (ps & 1) runs at s_setprio 1, so
+// older one, so waves 4-7 finish ~3.6 us later and the barrier after phase 1 waits for them (phase
+// probe: DESIGN.md).  In pass ps the half (w >> 2) == (ps & 1) runs at s_setprio 1, so
 // the half that lagged in pass 0 leads in pass 1 (DMA kernels).  (Round 5 measured the alternatives —
 // three other priority modes, the target words staged before the A prefetch or with the Wo slice,
 // the epilogue in scalar instead of packed fp32 ops, the odd dz row by a shift instead of d16_hi —
@@ -100,7 +100,7 @@ __device__ __forceinline__ uint32_t bf16_pack2(float a, float b) {
 // k per read).  (Measured and dropped with it: the target words by 4-B LDS-DMA as [row][NJ] — the
 // epilogue's strided reads cost more than the staging saved — and phase 2 with the operands swapped
 // for 16-B dWo stores: 32 rows x 32 B per store instruction ran slower than 2 x 128-B rows of
-// 4-B stores; tools/micro/dec_probe2.hip)
+// 4-B stores)
 template <int D, int BB, bool DMA, bool IMG = false>
 __global__ __launch_bounds__(NTH) void dec_bce_dw_kernel(DecOutP p) {
   constexpr int d = D, B = BB;
@@ -329,9 +329,6 @@ __global__ __launch_bounds__(NTH) void dec_bce_dw_kernel(DecOutP p) {
   // compiler counts no vmcnt for it — a later counted wait can only over-wait, never under-wait,
   // since this store is younger than every load it counts).  Lanes of columns past |V| carry an
   // offset beyond the descriptor's range: the hardware drops their stores (no branch)
-#ifdef DEC_DIAG_NODZ   // diagnostic builds only (tools/micro/dec_probe2.hip): no dz stores
-#define DEC_STORE_PAIR(PK, R2) do { (void)(PK); } while (0)
-#else
 #define DEC_STORE_PAIR(PK, R2)                                                                           \
   do {                                                                                                    \
     const uint32_t so0 = 2u * (uint32_t)((((R2) & 3) + 8 * ((R2) >> 2)) * LZ);                           \
@@ -340,7 +337,6 @@ __global__ __launch_bounds__(NTH) void dec_bce_dw_kernel(DecOutP p) {
     asm volatile("buffer_store_short_d16_hi %0, %1, %2, %3 offen" ::"v"(PK), "v"(zv), "s"(dz_rs), "s"(so1)   \
                  : "memory");                                                                             \
   } while (0)
-#endif
 #pragma unroll
   for (int ps = 0; ps < npass; ++ps) {
     if (!RING1 && ps + 1 < npass) load_a(af[(ps + 1) & 1], ps + 1);

@@ -27,15 +27,6 @@
 
 #include "common.hpp"
 
-// diagnostic builds only (tools/micro/kl_probe_full.hip): the register path without its dZ stores /
-// its M~ loads (wrong results; what they cost)
-#ifndef KL_DIAG_NOSTORE
-#define KL_DIAG_NOSTORE 0
-#endif
-#ifndef KL_DIAG_NOMT
-#define KL_DIAG_NOMT 0
-#endif
-
 // dev-only timing hook (tools/micro/kl_probe.hip defines it); compiled out of the library
 #ifndef KL_PROBE
 #define KL_PROBE(k)
@@ -56,14 +47,9 @@ constexpr float PMIN = 1e-7f;
 // dWo slice between its per-tile read-modify-writes — 1,620 -> 1,500 us per block
 // (tools/micro/kl_probe_full.hip; either alone gains ~1 %).  One tile (the sampled regulariser):
 // default — the non-temporal pair slowed its epilogues (p1 4.9 -> 6.8 us).
+// The 16-B dZ row stores take the pass's policy too (default policy for them measured 2,378 vs
+// 2,199-2,206 us/step, r05zo: the non-temporal stores carry the gain).
 constexpr int KL_CPOL_NT = 2;  // the SLC/NT bit of the buffer instructions' cache-policy operand
-#ifndef KL_ZST_CPOL
-#define KL_ZST_CPOL -1   // build knob: the 16-B dZ row stores' policy (-1: the pass's CPOL; 0 measured
-                         // 2,378 vs 2,199-2,206 us/step, r05zo: the non-temporal stores carry the gain)
-#endif
-#ifndef KL_SEP_CPOL
-#define KL_SEP_CPOL KL_CPOL_NT   // build knob: the main pass's policy with dWo in its own kernel
-#endif
 constexpr float LN_PMIN = -16.11809565095832f;  // ln(1e-7)
 
 
@@ -341,9 +327,6 @@ __global__ __launch_bounds__(NTH) __attribute__((amdgpu_waves_per_eu(1, 2))) voi
 // fragment reloaded for the wave's next row block right after its MFMAs: registers for the 6
 // accumulators).  Per 96-column slice the MFMA order, the max and the sum are kl_stats_kernel's:
 // the same partials bit for bit.  Grid: ceil(nsl / 2) slice pairs x 2 row halves.
-#ifndef CCREC_KL_STATS2
-#define CCREC_KL_STATS2 1   // build knob (A/B builds): 0 = kl_stats_kernel for every shape
-#endif
 __global__ __launch_bounds__(NTH) __attribute__((amdgpu_waves_per_eu(1, 2))) void kl_stats2_kernel(KlP p) {
   constexpr int D = 256, NB = kl_nb<D>(), NJ = NB / 32, CHD = D / 8, nkk = D / 16, W8 = NTH / 64;
   __shared__ __attribute__((aligned(16))) bf16_t Wt[2][NB * D];
@@ -541,7 +524,7 @@ __device__ __forceinline__ void kl_slice(const KlP &p, const int sl, bf16_t *Wt,
   // WSX (PF with M~ in registers; the launcher checks |V| % 8 == 0 and the offsets' range): dZ leaves
   // through the free dZ^T LDS as 16-B row stores.  The accumulator layout gives a lane one column
   // of 16 rows, so a direct store writes 2 B per lane — 48 buffer_store_short per lane and pass,
-  // issue-bound (the pass without its dZ stores ran ~20 % faster, kl_probe_full KL_DIAG_NOSTORE).
+  // issue-bound (the pass without its dZ stores ran ~20 % faster, a diagnostic build).
   // Instead adjacent lanes pair their bf16 values by one DPP swap into row-major dwords, the wave
   // writes its [32][96] tile to a private LDS image (208-B pitch: no bank conflicts between the
   // half-waves' rows), reads it back as 16-B row chunks and stores 6 x 16 B per lane.
@@ -604,8 +587,7 @@ __device__ __forceinline__ void kl_slice(const KlP &p, const int sl, bf16_t *Wt,
           const uint32_t gc4 = 4u * (uint32_t)(n0 + j * 32 + (lane & 31));
 #pragma unroll
           for (int r = 0; r < 16; ++r)
-            tv[j][r] = KL_DIAG_NOMT ? (float)(r + j) * 1e-3f
-                                    : __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(mt_rs, roff[r] + gc4, 0, CPOL));
+            tv[j][r] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(mt_rs, roff[r] + gc4, 0, CPOL));
         }
       }
       __builtin_amdgcn_sched_barrier(0);
@@ -669,7 +651,7 @@ __device__ __forceinline__ void kl_slice(const KlP &p, const int sl, bf16_t *Wt,
             tt[r] = zb;
             cs[j] += dzf;  // the bias gradient sums the fp32 dz
             // the lane part of the offset in a VGPR, the row part (r) as the scalar soffset
-            if constexpr (!WSX && !KL_DIAG_NOSTORE)
+            if constexpr (!WSX)
               __builtin_amdgcn_raw_buffer_store_b16(zb, dz_rs, 2u * (zrow + (uint32_t)(j * 32)),
                                                     2u * (uint32_t)(((r & 3) + 8 * (r >> 2)) * V), CPOL);
             if (r & 1) ws_pair(r, tt[r - 1], zb);
@@ -728,7 +710,7 @@ __device__ __forceinline__ void kl_slice(const KlP &p, const int sl, bf16_t *Wt,
           const v4u x = *reinterpret_cast<const v4u *>(zimg + row * WS_PITCH + ch * 4);
           const uint32_t off = n0 + 8 * ch < V ? 2u * ((uint32_t)(t0 + rb + row) * (uint32_t)V + (uint32_t)(n0 + 8 * ch))
                                                : 0x80000000u;
-          __builtin_amdgcn_raw_buffer_store_b128(x, dz_rs, off, 0, KL_ZST_CPOL < 0 ? CPOL : KL_ZST_CPOL);
+          __builtin_amdgcn_raw_buffer_store_b128(x, dz_rs, off, 0, CPOL);
         }
       }
 
@@ -938,15 +920,6 @@ __global__ __launch_bounds__(NTH) void kl_fix_kernel(KlP p) {
 // (Staged by LDS-DMA instead, the compiler waits for every outstanding copy — vmcnt(0) — before
 // each chunk's LDS reads, so nothing stays in flight.)
 constexpr int DW_NB = 96, DW_KC = 128;
-// build knob (A/B): kl_dwo_kernel's B fragments one k step ahead
-#ifndef DWO_BPF
-#define DWO_BPF 1
-#endif
-// dev diagnostics (tools/micro/dwo_diag.hip; 0 in the library): 1 no MFMA, 2 no B reads, 4 no dZ
-// loads, 8 no A loads
-#ifndef DWO_DIAG
-#define DWO_DIAG 0
-#endif
 template <int D, bool V8>
 __global__ __launch_bounds__(NTH) void kl_dwo_kernel(KlP p) {
   constexpr int NB = DW_NB, NJ = NB / 32, KC = DW_KC, KS = KC / 16;
@@ -969,7 +942,6 @@ __global__ __launch_bounds__(NTH) void kl_dwo_kernel(KlP p) {
   // 24 KB in flight per CU, ~2.7 TB/s)
   v4u stg0[NPC], stg1[NPC];
   auto gload = [&](v4u (&stg)[NPC], int c) {
-    if constexpr (DWO_DIAG & 4) return;
 #pragma unroll
     for (int u = 0; u < NPC; ++u) {
       const int q = tid + NTH * u, r = q / PPR, e = q % PPR;
@@ -990,7 +962,6 @@ __global__ __launch_bounds__(NTH) void kl_dwo_kernel(KlP p) {
   const bf16_t *abase = p.D3tp + ((int64_t)min(wt, D / 32 - 1) * (p.ldt / 16) * 64 + lane) * 8;
   const int k0 = p.row0 / 16, klast = (p.row0 + p.rows) / 16 - 1;
   auto load_a = [&](bf16x8_t (&dst)[KS], int c) {
-    if constexpr (DWO_DIAG & 8) return;
 #pragma unroll
     for (int ks = 0; ks < KS; ++ks)
       dst[ks] = *reinterpret_cast<const bf16x8_t *>(abase + (int64_t)min(k0 + c * KS + ks, klast) * 512);
@@ -1024,41 +995,27 @@ __global__ __launch_bounds__(NTH) void kl_dwo_kernel(KlP p) {
     if (active) {
       const bf16_t *Zc = Zs[st];
       auto bfrag = [&](int ks, int j) {
-        if constexpr (DWO_DIAG & 2) return cur[(ks + j) % KS];
         const bf16_t *tb = Zc + (ks * 16 + 8 * half + ((lane >> 2) & 3)) * NB + j * 32 + 16 * ((lane >> 4) & 1) + 4 * (lane & 3);
         const v4s lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) v4s *)tb);
         const v4s hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) v4s *)(tb + 4 * NB));
         return __builtin_bit_cast(bf16x8_t, __builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7));
       };
-      if constexpr (DWO_BPF) {
-        // B fragments one k step ahead (two register sets): the k step's MFMAs wait on reads issued
-        // a whole step earlier, not on the ones just before them
-        bf16x8_t bq[2][NJ];
+      // B fragments one k step ahead (two register sets): the k step's MFMAs wait on reads issued
+      // a whole step earlier, not on the ones just before them
+      bf16x8_t bq[2][NJ];
 #pragma unroll
-        for (int j = 0; j < NJ; ++j) bq[0][j] = bfrag(0, j);
+      for (int j = 0; j < NJ; ++j) bq[0][j] = bfrag(0, j);
 #pragma unroll
-        for (int ks = 0; ks < KS; ++ks) {
-          if (ks + 1 < KS) {
+      for (int ks = 0; ks < KS; ++ks) {
+        if (ks + 1 < KS) {
 #pragma unroll
-            for (int j = 0; j < NJ; ++j) bq[(ks + 1) & 1][j] = bfrag(ks + 1, j);
-          }
-          __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-          for (int j = 0; j < NJ; ++j) {
-            if constexpr (DWO_DIAG & 1) {
-              acc[j][0] += __builtin_bit_cast(float, __builtin_shufflevector(bq[ks & 1][j], bq[ks & 1][j], 0, 1));
-              acc[j][1] += __builtin_bit_cast(float, __builtin_shufflevector(cur[ks], cur[ks], 0, 1));
-            } else {
-              acc[j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(cur[ks], bq[ks & 1][j], acc[j], 0, 0, 0);
-            }
-          }
-          __builtin_amdgcn_sched_barrier(0);
+          for (int j = 0; j < NJ; ++j) bq[(ks + 1) & 1][j] = bfrag(ks + 1, j);
         }
-      } else {
+        __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
-        for (int ks = 0; ks < KS; ++ks)
-#pragma unroll
-          for (int j = 0; j < NJ; ++j) acc[j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(cur[ks], bfrag(ks, j), acc[j], 0, 0, 0);
+        for (int j = 0; j < NJ; ++j)
+          acc[j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(cur[ks], bq[ks & 1][j], acc[j], 0, 0, 0);
+        __builtin_amdgcn_sched_barrier(0);
       }
     }
     lds_barrier();   // chunk c + 1 written; chunk c read (its stage is rewritten next)
@@ -1083,13 +1040,13 @@ __global__ __launch_bounds__(NTH) void kl_dwo_kernel(KlP p) {
 // ---- dWo in wide slices (the default for d = 256, |V| % 8 == 0): kl_dwo_kernel spends its time
 // on the per-CU operand streams, not on the MFMAs: every 96-column block re-reads the whole packed
 // D3^T (11 MB at the full-mode shape — 2.7x the block's dZ bytes) and each of its 8 waves reads the
-// whole dZ chunk from LDS (tools/micro/dwo_diag.hip: the D3^T loads alone 134 us of its 345).
+// whole dZ chunk from LDS (measured in a diagnostic build: the D3^T loads alone 134 us of its 345).
 // Here a block owns a 192-column slice and HALF of the rows (K split in two: 2 x 115 blocks), eight
 // waves (two per SIMD) of 32 rows of d x all 192 columns (6 accumulator tiles): per column, half
 // the D3^T bytes of kl_dwo_kernel.  dZ chunks of 128 rows x 192 columns (48 KB) are copied
 // global -> LDS by 16-B LDS-DMA (non-temporal: read once) two chunks ahead of use in a ring of
 // three stages; A fragments (8 k steps per wave) load one chunk ahead into registers.
-// Measured alone at the full-mode shape (tools/micro/dwo_diag.hip, r05z): 242 us + 13 us for the
+// Measured alone at the full-mode shape (r05z): 242 us + 13 us for the
 // halves' sum vs kl_dwo_kernel's 343; four waves of 64 rows (accumulators in AGPRs, one wave per
 // SIMD) 273, default cache policy on the copies 264, copies issued before the A loads (one chunk
 // of effective lead: the in-order wait for A(c) also waited for DMA(c + 1)) 294.  Both streams are inline asm with counted waits written here (the
@@ -1100,21 +1057,7 @@ __global__ __launch_bounds__(NTH) void kl_dwo_kernel(KlP p) {
 // partial tile goes to the workspace, the second's to gW, and kl_dwo2_sum_kernel adds them (an
 // arrival ticket per slice with the second block adding instead cost ~100 us: the agent-scope
 // fences' L2 write-back / invalidate under the still-streaming blocks).
-#ifndef CCREC_DWO2
-#define CCREC_DWO2 1   // build knob (A/B builds): 0 = dWo by the 96-column kernels always
-#endif
-// dev diagnostics (tools/micro/dwo_diag.hip; 0 in the library): 2 no MFMA, 4 no dZ DMA, 8 no A
-// loads
-#ifndef DW2_DIAG
-#define DW2_DIAG 0
-#endif
-#ifndef DW2_CPOL
-#define DW2_CPOL KL_CPOL_NT   // build knob: the dZ copies' cache policy (0: default)
-#endif
-#ifndef DW2_WAVES
-#define DW2_WAVES 8   // build knob: 8 waves of 32 rows of d (two per SIMD) or 4 of 64 (one per SIMD)
-#endif
-constexpr int DW2_NB = 192, DW2_KC = 128, DW2_NS = 3, DW2_NT = 64 * DW2_WAVES, DW2_SPLIT = 2;
+constexpr int DW2_NB = 192, DW2_KC = 128, DW2_NS = 3, DW2_NT = 64 * 8, DW2_SPLIT = 2;
 constexpr int DW2_STAGE = DW2_KC * DW2_NB * 2;          // 48 KB
 constexpr int DW2_LDS = DW2_NS * DW2_STAGE;             // 144 KB
 
@@ -1159,11 +1102,10 @@ __global__ __launch_bounds__(DW2_NT) void kl_dwo2_kernel(KlP p) {
   }
   const uint32_t lbase = lds_addr(dw2mem) + 1024u * (uint32_t)(NPW * w);
   auto dma = [&](int c) {
-    if constexpr (DW2_DIAG & 4) return;
     const uint32_t so = c < nch ? (uint32_t)(cb + c) * (uint32_t)KC * (uint32_t)V * 2u : 0x80000000u;
     const uint32_t base = lbase + (uint32_t)(c % NS) * (uint32_t)DW2_STAGE;
 #pragma unroll
-    for (int t = 0; t < NPW; ++t) dma_asm<16, DW2_CPOL>(zr, vo[t], so, base + 1024u * t);
+    for (int t = 0; t < NPW; ++t) dma_asm<16, KL_CPOL_NT>(zr, vo[t], so, base + 1024u * t);
   };
   // A fragment (band b, k step kk): the packed D3^T's 1-KB fragment (band NBD w + b, kk)
   uint32_t va[NBD];
@@ -1171,7 +1113,6 @@ __global__ __launch_bounds__(DW2_NT) void kl_dwo2_kernel(KlP p) {
   for (int b = 0; b < NBD; ++b) va[b] = ((uint32_t)(NBD * w + b) * (uint32_t)(p.ldt / 16) * 64u + (uint32_t)lane) * 16u;
   const int k0 = p.row0 / 16, klast = (p.row0 + p.rows) / 16 - 1;
   auto aload = [&](v4u (&dst)[NBD][KS], int c) {   // (c past the end: clamped, never used)
-    if constexpr (DW2_DIAG & 8) return;
 #pragma unroll
     for (int ks = 0; ks < KS; ++ks) {
       const uint32_t so = (uint32_t)min(k0 + (cb + c) * KS + ks, klast) * 1024u;
@@ -1232,12 +1173,8 @@ __global__ __launch_bounds__(DW2_NT) void kl_dwo2_kernel(KlP p) {
       for (int b = 0; b < NBD; ++b) {
         const bf16x8_t a = __builtin_bit_cast(bf16x8_t, cur[b][ks]);
 #pragma unroll
-        for (int j = 0; j < NJ; ++j) {
-          if constexpr (DW2_DIAG & 2)
-            acc[b][j][0] += __builtin_bit_cast(float, __builtin_shufflevector(bq[ks & 1][j], a, 0, 9));
-          else
-            acc[b][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, bq[ks & 1][j], acc[b][j], 0, 0, 0);
-        }
+        for (int j = 0; j < NJ; ++j)
+          acc[b][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, bq[ks & 1][j], acc[b][j], 0, 0, 0);
       }
       __builtin_amdgcn_sched_barrier(0);
     }
@@ -1378,10 +1315,10 @@ extern "C" int cc_dec_softmax_kl_dw(const cc_dec_kl_args *a, void *stream) {
   // the main pass's dZ through LDS as 16-B row stores (16-B aligned rows; the sentinel past range)
   const bool wstore = a->V % 8 == 0 && ((uintptr_t)a->dZ & 15) == 0 && (int64_t)a->rows * a->V * 2 < 0x80000000ll;
   // the stats in slice pairs x row halves (kl_stats2_kernel): many row tiles (full mode), d = 256
-  const bool stats2 = CCREC_KL_STATS2 && a->d == 256 && a->rows > TR;
+  const bool stats2 = a->d == 256 && a->rows > TR;
   // dWo in 192-column slices x two row halves (kl_dwo2_kernel): 16-B aligned rows, the chunk
   // sentinel 0x80000000 past dZ's range, at least one chunk per half
-  const bool dwo2 = CCREC_DWO2 && a->d == 256 && a->V % 8 == 0 && (((uintptr_t)a->dZ | (uintptr_t)a->gW) & 15) == 0 &&
+  const bool dwo2 = a->d == 256 && a->V % 8 == 0 && (((uintptr_t)a->dZ | (uintptr_t)a->gW) & 15) == 0 &&
                     (int64_t)a->rows * a->V * 2 < 0x80000000ll && cdiv(a->rows, DW2_KC) >= DW2_SPLIT &&
                     p.dw_part && !(a->flags & CC_KL_DWO_NARROW);
 #define KL_LAUNCH(DD)                                                                                          \
@@ -1395,9 +1332,9 @@ extern "C" int cc_dec_softmax_kl_dw(const cc_dec_kl_args *a, void *stream) {
     CC_LAUNCH_CHECK("kl_merge_kernel");                                                                      \
     if (dw_sep) {                                                                                            \
       if (wstore)                                                                                            \
-        hipLaunchKernelGGL((kl_main_kernel<DD, KL_SEP_CPOL, false, (DD <= 256)>), gm, dim3(NTH), 0, s, p);    \
+        hipLaunchKernelGGL((kl_main_kernel<DD, KL_CPOL_NT, false, (DD <= 256)>), gm, dim3(NTH), 0, s, p);    \
       else                                                                                                   \
-        hipLaunchKernelGGL((kl_main_kernel<DD, KL_SEP_CPOL, false>), gm, dim3(NTH), 0, s, p);                 \
+        hipLaunchKernelGGL((kl_main_kernel<DD, KL_CPOL_NT, false>), gm, dim3(NTH), 0, s, p);                 \
       CC_LAUNCH_CHECK("kl_main_kernel");                                                                     \
       hipLaunchKernelGGL((kl_fix_kernel<DD, false>), dim3(FIXG), dim3(NTH), 0, s, p);                       \
       CC_LAUNCH_CHECK("kl_fix_kernel");                                                                      \

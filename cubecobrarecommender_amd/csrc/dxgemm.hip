@@ -21,11 +21,6 @@
 
 #include "common.hpp"
 
-// build knob (A/B builds: CCREC_EXTRA_FLAGS=-DCCREC_DX_WIDE_MIN=..., a tagged library; no run-time switch)
-#ifndef CCREC_DX_WIDE_MIN
-#define CCREC_DX_WIDE_MIN 4096
-#endif
-
 namespace {
 
 constexpr int XBM = 128, XBN = 128, XBK = 64, XST = 4, XNT = 256;
@@ -152,11 +147,6 @@ __global__ __launch_bounds__(XNT) void dx_splitk_kernel(DxP p) {
 // B 256 x 64 (48 KB each).  Splits are dealt split-major over the XCDs as above, so a split's Wo
 // panel (256 x K/splits bf16) stays in one XCD's L2.
 constexpr int WBM = 128, WBN = 256, WST = 3, WNT = 512;
-// dev diagnostics (tools/micro/dx_diag.hip; 0 in the library): 1 no Wo copies / fragment loads, 2 no dZ
-// copies, 4 no MFMA (dx_wide_kernel and dx_wide3_kernel)
-#ifndef DXW_DIAG
-#define DXW_DIAG 0
-#endif
 constexpr int WTILE_BYTES = (WBM + WBN) * XBK * 2;  // 48 KB
 constexpr int WLDS = WST * WTILE_BYTES;              // 144 KB
 
@@ -170,7 +160,6 @@ __device__ __forceinline__ void dma_tile_w(const DxP &p, const __amdgpu_buffer_r
   char *sa = smem + st * WTILE_BYTES, *sb = sa + WBM * XBK * 2;
 #pragma unroll
   for (int u = 0; u < 2; ++u) {
-    if constexpr (DXW_DIAG & 2) break;
     const int i = w * 2 + u;  // A rows 8i .. 8i + 7
     const int row = 8 * i + rl;
     const int k = k0 + 8 * (slot ^ ((row >> 1) & 7));
@@ -179,7 +168,6 @@ __device__ __forceinline__ void dma_tile_w(const DxP &p, const __amdgpu_buffer_r
   }
 #pragma unroll
   for (int u = 0; u < 4; ++u) {
-    if constexpr (DXW_DIAG & 1) break;
     const int i = w * 4 + u;  // B rows 8i .. 8i + 7
     const int row = 8 * i + rl;
     const int k = k0 + 8 * (slot ^ ((row >> 1) & 7));
@@ -224,11 +212,6 @@ __global__ __launch_bounds__(WNT) void dx_wide_kernel(DxP p) {
     const char *sa = wsmem + (t % WST) * WTILE_BYTES, *sb = sa + WBM * XBK * 2;
 #pragma unroll
     for (int kk = 0; kk < XBK / 16; ++kk) {
-      if constexpr (DXW_DIAG & 4) {
-        const int c = 2 * kk + half;
-        acc[0][0][0] += __builtin_bit_cast(float, __builtin_shufflevector(frag(sa, ar, c), frag(sb, br, c), 0, 9));
-        continue;
-      }
       const int c = 2 * kk + half;
       const bf16x8_t a0 = frag(sa, ar, c), a1 = frag(sa, ar + 32, c);
       const bf16x8_t b0 = frag(sb, br, c), b1 = frag(sb, br + 32, c);
@@ -261,13 +244,8 @@ __global__ __launch_bounds__(WNT) void dx_wide_kernel(DxP p) {
 // then DMA(t + 2), so the counted wait for B(t) does not wait on the newest copies; copies and
 // loads past the end use the range sentinel (zeros, no traffic) so every iteration issues the same
 // count.  The MFMA chain per output is the other paths' (bit-identical partials).
-#ifndef DX3_LEAD
-#define DX3_LEAD 2   // build knob: dZ K-tiles copied ahead of the one multiplied (stages = lead + 1)
-#endif
-#ifndef DX3_CPOL
-#define DX3_CPOL 0   // build knob: the dZ copies' cache policy (default; nt measured 343 vs 304 us)
-#endif
-constexpr int W3L = DX3_LEAD, W3ST = W3L + 1, W3NT = 512;
+// W3L: dZ K-tiles copied ahead of the one multiplied (stages = lead + 1)
+constexpr int W3L = 2, W3ST = W3L + 1, W3NT = 512;
 static_assert(W3L >= 2 && W3L <= 5, "dx_wide3: the startup waits below are written for leads 2..5");
 
 template <int N>
@@ -287,7 +265,6 @@ __global__ __launch_bounds__(W3NT) void dx_wide3_kernel(DxP p) {
   const __amdgpu_buffer_rsrc_t rb = __builtin_amdgcn_make_buffer_rsrc((void *)p.B, (short)0, p.b_bytes, 0x00020000);
   const int rl = lane >> 3, slot = lane & 7;
   auto dma = [&](int t) {   // dZ K-tile t -> stage t % W3ST: 2 instructions of 8 rows x 128 B per wave
-    if constexpr (DXW_DIAG & 2) return;
     char *sa = w3mem + (t % W3ST) * W3TILE;
     const int k0 = kbeg + t * XBK;
 #pragma unroll
@@ -295,14 +272,13 @@ __global__ __launch_bounds__(W3NT) void dx_wide3_kernel(DxP p) {
       const int i = w * 2 + u, row = 8 * i + rl;
       const int k = k0 + 8 * (slot ^ ((row >> 1) & 7));
       const uint32_t oa = k < kend ? (uint32_t)(((bm + row) * p.lda + k) * 2) : 0x80000000u;
-      __builtin_amdgcn_raw_ptr_buffer_load_lds(ra, (lds_void *)(sa + i * 1024), 16, oa, 0, 0, DX3_CPOL);   // dZ: default policy (knob)
+      __builtin_amdgcn_raw_ptr_buffer_load_lds(ra, (lds_void *)(sa + i * 1024), 16, oa, 0, 0, 0);   // dZ: default policy (nt measured 343 vs 304 us)
     }
   };
   // fragment (band, k step) of the packed image: 1 KB at (band * nks + k step) KB, lane L's 16 B at 16 L
   const int nks = (p.K + 15) / 16;
   const uint32_t bbase = (uint32_t)((bn / 32 + w) * nks) * 1024u + 16u * (uint32_t)lane;
   auto bload = [&](bf16x8_t (&dst)[XBK / 16], int t) {   // Wo fragments of K-tile t
-    if constexpr (DXW_DIAG & 1) return;
     const int k0 = kbeg + t * XBK;
 #pragma unroll
     for (int ks = 0; ks < XBK / 16; ++ks) {
@@ -347,12 +323,8 @@ __global__ __launch_bounds__(W3NT) void dx_wide3_kernel(DxP p) {
     for (int ks = 0; ks < XBK / 16; ++ks) {
       const int c = 2 * ks + half;
 #pragma unroll
-      for (int i = 0; i < 4; ++i) {
-        if constexpr (DXW_DIAG & 4)
-          acc[i][0] += __builtin_bit_cast(float, __builtin_shufflevector(frag(sa, ar + 32 * i, c), cur[ks], 0, 9));
-        else
-          acc[i] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(frag(sa, ar + 32 * i, c), cur[ks], acc[i], 0, 0, 0);
-      }
+      for (int i = 0; i < 4; ++i)
+        acc[i] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(frag(sa, ar + 32 * i, c), cur[ks], acc[i], 0, 0, 0);
     }
   };
   int t = 0;
@@ -463,8 +435,8 @@ extern "C" int cc_gemm_dx_splitk(const void *A, int32_t lda, const void *B, int3
   p.tiles_m = M / XBM;
   p.a_bytes = (uint32_t)((int64_t)M * lda * 2);
   p.b_bytes = (uint32_t)((int64_t)N * ldb * 2);
-  constexpr int wide_min = CCREC_DX_WIDE_MIN;  // build knob: smallest M for the 128 x 256 tiles (0: never)
-  if (wide_min > 0 && M >= wide_min && N % WBN == 0) {  // tall M (full-mode regulariser)
+  constexpr int wide_min = 4096;  // smallest M for the 128 x 256 tiles
+  if (M >= wide_min && N % WBN == 0) {  // tall M (full-mode regulariser)
     static bool attr = [] {
       return hipFuncSetAttribute((const void *)dx_wide_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, WLDS) ==
              hipSuccess;

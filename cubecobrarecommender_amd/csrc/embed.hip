@@ -19,24 +19,6 @@
 #include "tower_dw_dev.hpp"
 #include "xt.hpp"
 
-// build knobs (A/B builds: CCREC_EXTRA_FLAGS=-D..., a tagged library; the library reads no
-// environment): the gather / scatter variants below default to the measured-fastest ones
-#ifndef CCREC_GATHER2
-#define CCREC_GATHER2 48
-#endif
-#ifndef CCREC_GATHER_XCDW
-#define CCREC_GATHER_XCDW 44
-#endif
-#ifndef CCREC_GATHER_XCD
-#define CCREC_GATHER_XCD 44
-#endif
-#ifndef CCREC_GATHER_U
-#define CCREC_GATHER_U 8
-#endif
-#ifndef CCREC_SCATTER_U
-#define CCREC_SCATTER_U 8
-#endif
-
 // dev-only timing hook (tools/micro/eg_probe.hip defines it); compiled out of the library
 #ifndef EG_PROBE
 #define EG_PROBE(k)
@@ -84,10 +66,7 @@ __device__ __forceinline__ void load_row(const T *__restrict__ p, float (&v)[EPL
 // with U row loads in flight per lane; the four partials are added in wave order (deterministic).
 constexpr int GW = 4;
 // E1 backward: waves per W1 row (measured: 2 -> 49 us, 4 -> 46, 8 -> 62, 16 -> 130 at cfg 2).
-#ifndef CCREC_SCATTER_GW
-#define CCREC_SCATTER_GW 4
-#endif
-constexpr int SGW = CCREC_SCATTER_GW;
+constexpr int SGW = 4;
 
 // The row's index list is staged in LDS first (one coalesced read), so each batch of U row
 // loads costs one dependent global round trip instead of two.
@@ -757,18 +736,10 @@ __global__ __launch_bounds__(256, 2) void embed_grad_pk_kernel(const bf16_t *__r
 // extra launch).
 constexpr int CS_NT = 512;                     // 8 waves, ~one block per CU
 // config 5's instance (XWM = 32, R = 1024, TF Adam in the epilogue): tiles per wave, the Adam-operand
-// prefetch and the k-steps per fragment group trade registers (build-time A/B knobs)
-#ifndef EG_TPW32
-#define EG_TPW32 3
-#endif
-#ifndef EG_PF_XWM
-#define EG_PF_XWM 16
-#endif
-#ifndef EG_CSG32
-#define EG_CSG32 4
-#endif
-constexpr int cs_tpw(int xwm, bool adam = false) {  // tiles per wave (registers)
-  return xwm <= 16 ? 3 : xwm <= 32 ? (adam ? EG_TPW32 : 3) : 1;
+// prefetch and the k-steps per fragment group trade registers; 3 tiles, no prefetch and groups of 4
+// measured fastest, so that instance is shaped like the others
+constexpr int cs_tpw(int xwm, bool adam = false) {  // tiles per wave (registers); the same with Adam
+  return xwm <= 32 ? 3 : 1;
 }
 // byte -> 8 bf16 (16 B) LUT lane copies: fewer where the LDS is short (R > 512 with the Adam
 // epilogue's re-layout tiles, R > 1024): 2-way bank conflicts at 8 copies
@@ -801,24 +772,12 @@ __device__ __forceinline__ uint4 byte_bf16(uint32_t e) {  // 8 bits -> 8 bf16 of
   return make_uint4(w[0], w[1], w[2], w[3]);
 }
 // the W1 Adam epilogue's p / m / v streams (read and written once per step): cache policy.
-// Non-temporal measured slower (W1 kernel 32 -> 41 us in the BCE step, r03 A/B): default.
-#ifndef EG_ADAM_NT
-#define EG_ADAM_NT 0
-#endif
-__device__ __forceinline__ cc_adam::f32x4_t eg_ld(const cc_adam::f32x4_t *q) {
-  if constexpr (EG_ADAM_NT) return __builtin_nontemporal_load(q);
-  else return *q;
-}
-__device__ __forceinline__ void eg_st(cc_adam::f32x4_t *q, cc_adam::f32x4_t v) {
-  if constexpr (EG_ADAM_NT) __builtin_nontemporal_store(v, q);
-  else *q = v;
-}
+// Non-temporal measured slower (W1 kernel 32 -> 41 us in the BCE step, r03 A/B): plain accesses.
+__device__ __forceinline__ cc_adam::f32x4_t eg_ld(const cc_adam::f32x4_t *q) { return *q; }
+__device__ __forceinline__ void eg_st(cc_adam::f32x4_t *q, cc_adam::f32x4_t v) { *q = v; }
 // ADAM: TF Adam on W1 in the tile epilogue (one process: the gradient is final here) — p, m, v
 // stream through once, the bf16 shadow is rewritten, the W1 gradient is never stored; the bias
 // row's gradient still goes to bias_grad for the main Adam launch
-#ifndef EG_PREFETCH
-#define EG_PREFETCH 1
-#endif
 struct CsAdam {
   float *p, *m, *v;      // W1 rows of the flat fp32 buffers ([V][d])
   bf16_t *shadow;        // W1 rows of the bf16 shadow
@@ -993,12 +952,12 @@ __global__ __launch_bounds__(CS_NT, 1) void embed_grad_cs_kernel(const bf16_t *_
   }
   // Adam operands of a tile's 16 elements per lane (unconditional: a clamped row, stored only for
   // real rows), double-buffered: tile i + 1's are issued before tile i's epilogue, so its load
-  // latency runs under that epilogue and tile i + 1's MFMAs (EG_PREFETCH, R <= 512: the taller
+  // latency runs under that epilogue and tile i + 1's MFMAs (R <= 512: the taller
   // instances have no registers left for the second buffer; else before the MFMAs)
   // (the Adam epilogue works on the tile re-laid through LDS: instruction g covers tile rows
   // 8 g .. 8 g + 7, lane l row 8 g + (l >> 3), columns 4 (l & 7) .. +3 — eight whole 128-B lines
   // per wave instruction instead of 32 partial ones)
-  constexpr bool PF = ADAM && EG_PREFETCH && XWM <= EG_PF_XWM;
+  constexpr bool PF = ADAM && XWM <= 16;
   constexpr int NBUF = PF ? 2 : 1;
   cc_adam::f32x4_t AP[NBUF][ADAM ? 4 : 1], AM[NBUF][ADAM ? 4 : 1], AV[NBUF][ADAM ? 4 : 1];
   auto issue_adam = [&](int t, int b) {
@@ -1081,7 +1040,7 @@ __global__ __launch_bounds__(CS_NT, 1) void embed_grad_cs_kernel(const bf16_t *_
     // ds_read_b128 of the staged slice.  Groups of CS_G k-steps: the next group's 2 CS_G reads are
     // issued (sched_barrier) before this group's MFMAs, so the LDS latency runs under them.  The
     // B address is made opaque per tile so the compiler does not hoist the whole slice into VGPRs.
-    constexpr int CS_G = (XWM == 32 && ADAM) ? EG_CSG32 : 4, NG = 2 * XWM / CS_G;
+    constexpr int CS_G = 4, NG = 2 * XWM / CS_G;
     uint32_t boff = (uint32_t)lane * 16u;  // byte offset of this lane's fragment slot in Bs
     asm volatile("" : "+v"(boff));
     auto fetch = [&](int g, bf16x8_t (&da)[CS_G], bf16x8_t (&db)[CS_G]) {
@@ -1558,10 +1517,9 @@ extern "C" int cc_embed_gather_fwd_xt(int32_t dtype, const void *table, const fl
   CC_REQUIRE(!state || bpe >= 1, "cc_embed_gather_fwd_warm: batches_per_epoch");
   CC_REQUIRE(!xt_bits || (x_bits && xt_rows >= 1 && xt_rows <= R),
              "cc_embed_gather_fwd_xt: xt_bits needs x_bits and 1 <= xt_rows <= R");
-  constexpr int g2 = CCREC_GATHER2;    // build knob: 16-B lanes, two rows per load; waves x loads
-  constexpr int gw = CCREC_GATHER_XCDW;  // build knob: XCD column-sliced gather at d = 512 / 1024 (0 = gather_kernel)
-  const bool xcdw = dtype == CC_BF16 && (d == 512 || d == 1024) && gw > 0 && R > 0 && R <= 4096;
-  if (state && !(dtype == CC_BF16 && d == 256 && g2 > 0) && !xcdw) {  // other kernels: a separate launch
+  // bf16 only: d = 256 -> gather_xcd / gather2, d = 512 / 1024 -> gather_xcdw (XCD column slices)
+  const bool xcdw = dtype == CC_BF16 && (d == 512 || d == 1024) && R > 0 && R <= 4096;
+  if (state && !(dtype == CC_BF16 && d == 256) && !xcdw) {  // other kernels: a separate launch
     if (int rc = cc_state_advance(state, bpe, stream)) return rc;
     state = nullptr;
   }
@@ -1573,42 +1531,32 @@ extern "C" int cc_embed_gather_fwd_xt(int32_t dtype, const void *table, const fl
   const int nxt = xt_bits ? (int)cdiv((V + 31) / 32, XT_TJ) : 0;  // xt transpose blocks
   const int epl = d / 64;
   hipStream_t s = as_stream(stream);
-  constexpr int gx = CCREC_GATHER_XCD;  // build knob: XCD column-sliced gather (0 = gather2); waves x loads
+  // XCD column-sliced gather, 4 waves x 4 loads in flight
   // (tall R — the full-mode regulariser's |V| one-card identity rows — stays on gather2: a block
   // per 64-column slice of a one-card row is mostly overhead; measured 48 -> 121 us at R = 22,528)
-  if (dtype == CC_BF16 && d == 256 && g2 > 0 && gx > 0 && !xt_bits && R <= 4096) {
+  if (dtype == CC_BF16 && d == 256 && !xt_bits && R <= 4096) {
     const dim3 gxg((unsigned)(cdiv(R, 2) * 8));
-#define GX(GWN, U) \
-  if (gx == GWN * 10 + U) hipLaunchKernelGGL((gather_xcd_kernel<GWN, U>), gxg, dim3(64 * GWN), 0, s, \
-                                             (const bf16_t *)table, bias, R, x_cnt, x_idx, x_cap, (bf16_t *)out, \
-                                             warm, warm_bytes, state, bpe); else
-    GX(4, 4) GX(4, 8) GX(2, 4) GX(2, 8) GX(8, 4) GX(8, 2)
-      return cc::fail(CC_ERR_UNSUPPORTED, "CCREC_GATHER_XCD: unknown variant (build knob)");
-#undef GX
+    hipLaunchKernelGGL((gather_xcd_kernel<4, 4>), gxg, dim3(64 * 4), 0, s, (const bf16_t *)table, bias, R, x_cnt,
+                       x_idx, x_cap, (bf16_t *)out, warm, warm_bytes, state, bpe);
     CC_LAUNCH_CHECK("gather_xcd_kernel");
     return CC_OK;
   }
   if (xcdw) {
     const int nxt8 = (int)cdiv(nxt, 8) * 8;
     const dim3 gwg((unsigned)(nxt8 + 8 * R));
-#define GW(D, GWN, U)                                                                                           \
-  if (d == D && gw == GWN * 10 + U)                                                                             \
-    hipLaunchKernelGGL((gather_xcdw_kernel<D, GWN, U>), gwg, dim3(64 * GWN), 0, s, (const bf16_t *)table, bias, \
-                       x_cnt, x_idx, x_cap, (bf16_t *)out, state, bpe, x_bits, V, xt_bits, xt_rows, nxt8);        \
-  else
-    GW(512, 4, 4) GW(512, 2, 8) GW(512, 4, 8) GW(1024, 4, 4) GW(1024, 2, 8) GW(1024, 4, 8)
-      return cc::fail(CC_ERR_UNSUPPORTED, "CCREC_GATHER_XCDW: unknown variant");
-#undef GW
+    if (d == 512)   // 4 waves x 4 loads in flight
+      hipLaunchKernelGGL((gather_xcdw_kernel<512, 4, 4>), gwg, dim3(64 * 4), 0, s, (const bf16_t *)table, bias, x_cnt,
+                         x_idx, x_cap, (bf16_t *)out, state, bpe, x_bits, V, xt_bits, xt_rows, nxt8);
+    else
+      hipLaunchKernelGGL((gather_xcdw_kernel<1024, 4, 4>), gwg, dim3(64 * 4), 0, s, (const bf16_t *)table, bias, x_cnt,
+                         x_idx, x_cap, (bf16_t *)out, state, bpe, x_bits, V, xt_bits, xt_rows, nxt8);
     CC_LAUNCH_CHECK("gather_xcdw_kernel");
     return CC_OK;
   }
-  if (dtype == CC_BF16 && d == 256 && g2 > 0) {
-#define G2(GWN, U) \
-  if (g2 == GWN * 10 + U) hipLaunchKernelGGL((gather2_kernel<GWN, U>), dim3((unsigned)(R + nxt)), dim3(64 * GWN), 0, s, \
-                                             (const bf16_t *)table, bias, R, x_cnt, x_idx, x_cap, (bf16_t *)out, \
-                                             warm, warm_bytes, state, bpe, x_bits, V, xt_bits, xt_rows);
-    G2(4, 4) G2(4, 8) G2(8, 4) G2(8, 8) G2(4, 6) G2(8, 6)
-#undef G2
+  if (dtype == CC_BF16 && d == 256) {  // 16-B lanes, two rows per load; 4 waves x 8 loads in flight
+    hipLaunchKernelGGL((gather2_kernel<4, 8>), dim3((unsigned)(R + nxt)), dim3(64 * 4), 0, s, (const bf16_t *)table,
+                       bias, R, x_cnt, x_idx, x_cap, (bf16_t *)out, warm, warm_bytes, state, bpe, x_bits, V, xt_bits,
+                       xt_rows);
     CC_LAUNCH_CHECK("gather2_kernel");
     return CC_OK;
   }
@@ -1616,18 +1564,7 @@ extern "C" int cc_embed_gather_fwd_xt(int32_t dtype, const void *table, const fl
     hipLaunchKernelGGL(xt_transpose_kernel, dim3((unsigned)nxt), dim3(256), 0, s, x_bits, V, xt_bits, xt_rows);
     CC_LAUNCH_CHECK("xt_transpose_kernel");
   }
-  constexpr int gu = CCREC_GATHER_U;  // build knob: row loads in flight per lane (bf16, d = 256);
-  //                                     measured at cfg 2: 8 -> 328.5 us/step, 16 -> 337, 32 -> 341
-  if (dtype == CC_BF16 && epl == 4 && (gu == 16 || gu == 32)) {
-    if (gu == 16)
-      hipLaunchKernelGGL((gather_kernel<bf16_t, 4, 16>), grid, block, 0, s, (const bf16_t *)table,
-                         bias, d, R, x_cnt, x_idx, x_cap, (bf16_t *)out);
-    else
-      hipLaunchKernelGGL((gather_kernel<bf16_t, 4, 32>), grid, block, 0, s, (const bf16_t *)table,
-                         bias, d, R, x_cnt, x_idx, x_cap, (bf16_t *)out);
-    CC_LAUNCH_CHECK("gather_kernel");
-    return CC_OK;
-  }
+  // 8 row loads in flight per lane (bf16, d = 256, measured at cfg 2: 8 -> 328.5 us/step, 16 -> 337, 32 -> 341)
 #define GATHER_CASE(E)                                                                              \
   case E:                                                                                           \
     if (dtype == CC_BF16)                                                                           \
@@ -1658,13 +1595,7 @@ extern "C" int cc_embed_scatter_bwd(const float *dpre, int32_t V, int32_t d, int
   CC_REQUIRE(d % 64 == 0 && d >= 64 && d <= 1024, "cc_embed_scatter_bwd: d must be 64..1024, %64");
   const dim3 grid((unsigned)(bias_grad ? V + 1 : V)), block(64 * SGW);
   hipStream_t s = as_stream(stream);
-  constexpr int su = CCREC_SCATTER_U;  // build knob: dPre row loads in flight per lane (d = 256);
-  //                                      measured at cfg 2: 8 -> 45.5 us, 16 -> 54.8
-  if (d == 256 && su == 16) {
-    hipLaunchKernelGGL((scatter_bwd_kernel<4, 16>), grid, block, 0, s, dpre, V, d, R, xt_bits, grad, bias_grad);
-    CC_LAUNCH_CHECK("scatter_bwd_kernel");
-    return CC_OK;
-  }
+  // 8 dPre row loads in flight per lane (d = 256, measured at cfg 2: 8 -> 45.5 us, 16 -> 54.8)
   switch (d / 64) {
     case 1: hipLaunchKernelGGL((scatter_bwd_kernel<1, 8>), grid, block, 0, s, dpre, V, d, R, xt_bits, grad, bias_grad); break;
     case 2: hipLaunchKernelGGL((scatter_bwd_kernel<2, 8>), grid, block, 0, s, dpre, V, d, R, xt_bits, grad, bias_grad); break;

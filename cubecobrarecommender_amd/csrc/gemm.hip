@@ -13,14 +13,6 @@
 
 #include "common.hpp"
 
-// build knobs (A/B builds: CCREC_EXTRA_FLAGS=-D..., a tagged library; the library reads no environment)
-#ifndef CCREC_NT_BM
-#define CCREC_NT_BM 0
-#endif
-#ifndef CCREC_GEMM_NT
-#define CCREC_GEMM_NT 1
-#endif
-
 namespace {
 
 constexpr int BM = 64, BN = 64, NT = 256;
@@ -271,7 +263,7 @@ __global__ __launch_bounds__(NT) void gemm_kernel(GemmParams p) {
 // ------------------------------------------------------------------ NT bf16 kernel
 // C = A B^T with both operands K-contiguous (A [M][K], B [N][K]) — the decoder output layer's
 // forward (D3 Wo^T), weight gradient (D3^T dZ via D3^T and dZ^T images) and input gradient
-// (dZ Wo^T, split-K).  BM x 128 tiles (BM = 128/256/512), BM/32 waves each owning 64x64 (2x2
+// (dZ Wo^T, split-K).  BM x 128 tiles (BM = 128: taller tiles measured slower), BM/32 waves each owning 64x64 (2x2
 // blocks of v_mfma_f32_32x32x16_bf16); with the decoder's M <= 512 one workgroup covers every row
 // of a 128-column panel, so each panel of Wo / dZ^T is read once and the per-tile fixed cost
 // (prologue, epilogue) is paid BM/128 times less often.  LDS double-buffered (one barrier per
@@ -279,13 +271,10 @@ __global__ __launch_bounds__(NT) void gemm_kernel(GemmParams p) {
 // rows hold BK bf16 = CH x 16 B chunks stored at chunk ^ (row & (CH-1)), so the rows a fragment
 // read touches spread over the banks.  Tiles are assigned XCD-aware: each XCD gets a contiguous
 // run, walking M fastest, so the M-tiles sharing one B panel hit the same L2.
-// Epilogue: post-op fp32 tile -> LDS (in passes of <= 256 rows) -> 16-B coalesced stores of
+// Epilogue: post-op fp32 tile -> LDS -> 16-B coalesced stores of
 // C / Cf rows and of C^T rows (BCE: dZ^T, the k-contiguous operand of dW = D3^T dZ).
 constexpr int NBN = 128;
 constexpr int SLD = NBN + 1;  // odd row pitch: column reads for C^T spread over the banks
-#ifndef NT_RING
-#define NT_RING 2
-#endif
 
 // T = bf16_t (v_mfma_f32_32x32x16_bf16) or uint8_t = MX-FP8 e4m3 codes with one E8M0 scale per
 // 32 K-elements of a row (v_mfma_scale_f32_32x32x64_f8f6f4).  A K-tile is 128 bytes of every row
@@ -294,7 +283,7 @@ template <int BM, typename T = bf16_t>
 struct NtCfg {
   static constexpr bool MX = sizeof(T) == 1;
   static constexpr int NTH = BM * 2;         // BM/32 waves of 64x64 outputs
-  static constexpr int BKB = BM >= 512 ? 64 : 128;   // bytes per row per K-tile
+  static constexpr int BKB = 128;              // bytes per row per K-tile
   static constexpr int EPC = 16 / (int)sizeof(T);    // elements per 16-B chunk
   static constexpr int BK = BKB / (int)sizeof(T);    // elements per K-tile
   static constexpr int CH = BKB / 16;         // 16-B chunks per LDS row
@@ -302,7 +291,7 @@ struct NtCfg {
   static constexpr int NA = (A_CH + NTH - 1) / NTH, NB = (B_CH + NTH - 1) / NTH;
   static constexpr int STAGE = (BM + NBN) * BKB;    // bytes per K-tile (A + B)
   static constexpr int SCL = MX ? 2 * (BM + NBN) * 4 : 0;  // scale words, double-buffered
-  static constexpr int SR = BM > 256 ? 256 : BM;     // rows per epilogue staging pass
+  static constexpr int SR = BM;                // rows per epilogue staging pass
   static constexpr int LDS = 2 * STAGE + SCL > SR * SLD * 4 ? 2 * STAGE + SCL : SR * SLD * 4;
 };
 
@@ -492,7 +481,7 @@ __device__ __forceinline__ void nt_body(const GemmParams &p, int tiles_m, int bi
   float cs = 0.f;
   // D-deep register ring: K-tiles t+1 .. t+D-1 are in flight while tile t's MFMAs run; LDS is
   // double-buffered: tile t lives in buffer t & 1.
-  constexpr int D = NT_RING;
+  constexpr int D = 2;
   const NtPlan<BM, T> pl(p, bm, bn);
   NtStage<BM, T> st[D];
   const int nk = kbeg < kend ? (int)cdiv(kend - kbeg, BK) : 0;
@@ -772,15 +761,10 @@ int launch_nt_bm(const cc_gemm_args *g, const GemmParams &p, hipStream_t s) {
   return CC_OK;
 }
 
-// Tile height: 128 rows by default (taller tiles read each B panel fewer times but measured
-// slower on the decoder shapes, tools/micro/gemm_bench.py); CCREC_NT_BM=256/512 selects them.
+// Tile height: 128 rows, measured fastest for the decoder shapes (K = 256 / 512 / split V; taller
+// tiles read each B panel fewer times but measured slower, tools/micro/gemm_bench.py)
 template <int EPI>
 int launch_nt(const cc_gemm_args *g, const GemmParams &p, hipStream_t s) {
-  constexpr int forced = CCREC_NT_BM;  // build knob for benchmarking tile heights (0: 128)
-  int bm = 128;  // measured fastest for the decoder shapes (K = 256 / 512 / split V)
-  if (forced == 128 || forced == 256 || forced == 512) bm = forced;
-  if (bm == 512) return launch_nt_bm<EPI, 512>(g, p, s);
-  if (bm == 256) return launch_nt_bm<EPI, 256>(g, p, s);
   return launch_nt_bm<EPI, 128>(g, p, s);
 }
 
@@ -973,8 +957,7 @@ static int gemm_params(const cc_gemm_args *g, GemmParams &p) {
 
 // bf16 with both operands K-contiguous and 16-B aligned rows: the 128x128 NT kernel
 static bool nt_path(const cc_gemm_args *g, const GemmParams &p) {
-  constexpr bool nt_enabled = CCREC_GEMM_NT;  // build knob for benchmarking the generic kernel
-  return nt_enabled && g->dtype == CC_BF16 && !g->ta && g->tb && p.vec_a && p.vec_b &&
+  return g->dtype == CC_BF16 && !g->ta && g->tb && p.vec_a && p.vec_b &&
          g->epilogue != CC_EPI_MASK;
 }
 

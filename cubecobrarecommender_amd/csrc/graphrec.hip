@@ -46,19 +46,10 @@
 #include "rowsort.hpp"
 #include "topn_tiles.hpp"
 
-// build knobs of the scoring kernel's A/B, defaults on: workgroups numbered through
-// cc_xcd_run, and the rows a lane keeps in flight when it owns two columns
-#ifndef CCREC_GRAPH_XCD
-#define CCREC_GRAPH_XCD 1
-#endif
-#ifndef CCREC_GRAPH_ROWS_IN_FLIGHT
-#define CCREC_GRAPH_ROWS_IN_FLIGHT 8
-#endif
-
 namespace {
 
 constexpr int GNT = 256;          // scoring workgroup: a tile of GNT * CPL columns
-constexpr int WIDE_U = CCREC_GRAPH_ROWS_IN_FLIGHT;
+constexpr int WIDE_U = 8;           // rows a lane keeps in flight when it owns two columns (A/B: DESIGN §4)
 constexpr int IDCH = 1024;        // cube ids staged in LDS at a time
 constexpr int WIDE_ROWS = 16;     // from this many cubes per call a lane owns two columns
 constexpr int SNT = 1024;         // ranking / counting workgroup
@@ -125,7 +116,7 @@ __global__ __launch_bounds__(GNT) void graph_score_kernel(
   __shared__ int32_t s_ids[IDCH];
   const int tid = threadIdx.x;
   // cube fastest: see the header
-  const int l = CCREC_GRAPH_XCD ? cc_xcd_run((int)blockIdx.x, (int)gridDim.x) : (int)blockIdx.x;
+  const int l = cc_xcd_run((int)blockIdx.x, (int)gridDim.x);  // (A/B against blockIdx.x: DESIGN §4)
   const int tile = l / R, r = l - tile * R;
   const int beg = row_ptr[r], n = row_ptr[r + 1] - beg;
   const int j0 = (tile * GNT + tid) * CPL;

@@ -29,15 +29,11 @@
 
 namespace {
 
-// MX8_QNS (build knob): 2 = K tiles of 128 in two LDS stages (one tile of lead); 4 = K tiles of 64
-// (one 32x32x64 step) in four stages, three tiles in flight while the fourth is multiplied.  Split-K
-// chunks stay multiples of 128 either way (the same partition, the same bits).
-#ifndef MX8_QNS
-#define MX8_QNS 2
-#endif
-constexpr int QNS = MX8_QNS;
-static_assert(QNS == 2 || QNS == 4, "MX8_QNS: 2 or 4");
-constexpr int QM = 256, QN = 256, QKB = QNS == 2 ? 128 : 64, QNT = 512;
+// QNS LDS stages of K tiles of QKB: two stages of 128 (one tile of lead; four stages of 64, three
+// tiles in flight while the fourth is multiplied, measured no faster).  Split-K chunks are multiples
+// of 128.
+constexpr int QNS = 2;
+constexpr int QM = 256, QN = 256, QKB = 128, QNT = 512;
 constexpr int QA_BYTES = QM * QKB, QB_BYTES = QN * QKB;
 constexpr int QSTAGE = QA_BYTES + QB_BYTES + (QM + QN) * 4;   // + each row's E8M0 word of the 128 k
 constexpr int QLDS = QNS * QSTAGE;  // 132 KB
@@ -135,7 +131,7 @@ constexpr int QDMA_PER_TILE = 2 * QNI + 1;
 constexpr int QRPI = 1024 / QKB;                // rows per instruction
 // (128-B rows: row >> 1 & 7 — see dxgemm.hip: under row & 7 the rows r and r + 8 of a ds_read_b128
 // lane group share a bank slot)
-__device__ __forceinline__ int q_swz(int row) { return QKB == 128 ? ((row >> 1) & 7) : ((row >> 2) & 3); }
+__device__ __forceinline__ int q_swz(int row) { return (row >> 1) & 7; }
 __device__ __forceinline__ void q_dma(const QP &p, const i32x4_t &ra, const i32x4_t &rb, const i32x4_t &rsa,
                                       const i32x4_t &rsb, char *smem, int st, int bm, int bn, int k0) {
   const int lane = threadIdx.x & 63, w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
@@ -226,8 +222,7 @@ __device__ __forceinline__ void q_body(const QP &p, int q, char *smem) {
     for (int j = 0; j < 2; ++j) wb[j] = sS[QM + br + 32 * j];
 #pragma unroll
     for (int kk = 0; kk < QKB / 64; ++kk) {
-      // (QKB = 64: kbeg % 128 == 0, so t's parity places the tile's 64 k in the scale word's 128)
-      const int c0 = 4 * kk + half, sh = QKB == 128 ? 8 * (2 * kk + half) : 8 * (2 * (t & 1) + half);
+      const int c0 = 4 * kk + half, sh = 8 * (2 * kk + half);
       i32x8_t b[2];
       int sb[2];
 #pragma unroll

@@ -15,10 +15,7 @@
 
 namespace ccnoise {
 
-#ifndef NOISE_NT
-#define NOISE_NT 256
-#endif
-constexpr int NT = NOISE_NT;   // threads per cube (and per Adam block of the Adam + F launch)
+constexpr int NT = 256;   // threads per cube (and per Adam block of the Adam + F launch)
 static_assert(NT % 64 == 0 && NT <= 1024, "whole waves");
 constexpr uint32_t KIND_NOISE = 0, KIND_CUT = 1, KIND_YCUT = 2, KIND_ADD = 3, KIND_ADD_FB = 4,
                    KIND_REG = 5;

@@ -291,9 +291,7 @@ __global__ __launch_bounds__(NT) void tower_bwd_chain_kernel(TowerP p) {
 // current layer's MFMAs run — weights do not depend on the activations, so every layer after
 // the first starts with its operands already in flight.
 constexpr int FNT = 512;  // 8 waves
-#ifndef TF_CPB   // cc_tower_bwd_chain_noise: cubes of F per 512-thread workgroup (2 or 4)
-#define TF_CPB 4
-#endif
+constexpr int TF_CPB = 4;  // cc_tower_bwd_chain_noise: cubes of F per 512-thread workgroup
 constexpr int FB = 16;    // fragments per tile: reduction length <= 256
 
 struct Frags {

@@ -251,7 +251,7 @@ def test_bce_epilogue(dtype):
 
 
 @pytest.mark.parametrize('dtype', [L.CC_F32, L.CC_BF16])
-@pytest.mark.parametrize('d', [64, 256, 512])
+@pytest.mark.parametrize('d', [64, 128, 256, 512, 1024])   # every d / 64 the launchers switch on
 def test_gather_and_scatter(dtype, d):
     rng = np.random.default_rng(d)
     V, R, cap = 3000, 50, 120
